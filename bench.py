@@ -9,6 +9,11 @@ weak 3x600x1000 images per GPU through ResNet-101-C4 + RPN + RoIAlign + the two 
 backward, fused SGD step (variant "S1"). Synthetic VOC-shaped inputs already resident in HBM,
 random-init weights of the real architecture. `value` = supervised images / second over ALL ranks (weak scaling: 2
 supervised images per GPU). Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times --steps steps and prints the line. `--full` adds the figures that take runs of their own
+after the timed region (idle-device host time, sustained clocks, roofline passes, fp32 / bf16x3 modes, CPU baseline).
+`--dump-outputs DIR` writes what the last timed step computed (losses, sampled gradients and updated parameters) as .npy files:
+the inputs, weights and sampling RNG are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -37,8 +42,15 @@ def parse():
     ap.add_argument("--depth", type=int, default=101)
     ap.add_argument("--variant", default="s1", choices=["s1", "s0"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure everything beyond the headline figure: the "
+                    "idle-device host time, the sustained-clock run, the roofline passes, the fp32 / bf16x3 mode figures and the CPU baseline "
+                    "(--no-roofline, --no-cpu-baseline and --sustain-steps trim these). Off: the run sets up, warms up, times --steps steps "
+                    "and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed "
+                    "as DIR/<name>.npy (float32): its losses, and a fixed seeded sample of the flat gradient buffer and of the updated "
+                    "parameters (same indices)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the roofline passes and the fp32 / bf16x3 mode figures")
     ap.add_argument("--no-overlap", action="store_true", help="single HIP stream for the whole run (profiling aid: every "
                     "kernel's rocprof duration is then that kernel alone)")
     ap.add_argument("--graph", action="store_true", help="capture the whole step in a hipGraph and replay it (engine.GraphedStep; "
@@ -48,8 +60,8 @@ def parse():
                     "(default: engine.ReplayedStep -- the eager step's C-ABI call sequence recorded once per batch key and re-issued by one C call per "
                     "segment, csrc/replay.hip: the eager four-stream schedule without the interpreter), eager (Python issues every launch), graph "
                     "(= --graph: hipGraph replay)")
-    ap.add_argument("--sustain-steps", type=int, default=300, help="N=1: after the timed region the same step runs this many more times and the last "
-                    "two thirds are timed (`sustained_images_per_sec`: held clocks next to the burst figure); 0 = skip")
+    ap.add_argument("--sustain-steps", type=int, default=300, help="--full, N=1: after the timed region the same step runs this many more times and "
+                    "the last two thirds are timed (`sustained_images_per_sec`: held clocks next to the burst figure); 0 = skip")
     ap.add_argument("--early-update", action="store_true", help="per-bucket optimizer updates beside the backward instead of one "
                     "update after it (engine.EarlyUpdate; measured 18.56 vs 18.43 ms per step: off by default)")
     ap.add_argument("--high-priority", action="store_true", help="run the steps on a high-priority HIP stream instead of PyTorch's default stream "
@@ -124,6 +136,26 @@ def pick_exchange(table):
         return None
     best = min(ok)
     return table[best[1]]
+
+
+DUMP_SAMPLE = 1 << 20          # elements --dump-outputs takes from each flat buffer (4 MB apiece in float32)
+
+
+def dump_outputs(out_dir, losses, store):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files -- its losses (fp32[9], modeling.rcnn.LOSS_NAMES), and the
+    flat gradient buffer and the parameters after its SGD update at one fixed seeded sample of indices (the same for both buffers and for
+    every run of a model of this size)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = store.params.numel()
+    if n <= DUMP_SAMPLE:
+        idx = torch.arange(n)
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    idx = idx.to(store.params.device)
+    arrays = {"losses": losses, "grads_sample": store.grads.index_select(0, idx), "params_sample": store.params.index_select(0, idx)}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def _thread_cpu():
@@ -599,6 +631,10 @@ def main():
         print(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks; refusing to print a line whose n_gpus is not "
               "what was asked for", file=sys.stderr)
         return 2
+    if args.dump_outputs and (args.config not in (None, "r50_s1") or args.shapes != "fixed"):
+        print("bench.py: --dump-outputs writes the fixed-shape training step's outputs (no --shapes voc, no --config other than r50_s1)",
+              file=sys.stderr)
+        return 2
     claim_stdout()
     if args.dry_launch:
         keys = ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "HSA_ENABLE_IPC_MODE_LEGACY")
@@ -773,26 +809,30 @@ def main():
     cpu_ms = (time.process_time() - c0) / args.steps * 1e3          # CPU time of this process (all threads) per step over the timed region, waits included
     th1 = _thread_cpu()
     cpu_threads = sorted(((round((th1[t][1] - th0.get(t, (None, 0.0))[1]) / args.steps * 1e3, 3), th1[t][0]) for t in th1), reverse=True)[:4]
+    if args.dump_outputs and rank == 0:          # before any further step changes the buffers
+        dump_outputs(args.dump_outputs, losses, model.store)
+        _trace(f"outputs written to {args.dump_outputs}")
+    # everything below up to the result line runs with --full only (the plain line is the timed region's)
     # the host's OWN share of a step: the same step enqueued onto an IDLE device (synchronize before, clock stopped before anything is waited
     # for). `host_wall_ms_per_step_timed_region` below is the timed region's figure and includes waiting: the runtime's queues hold a few
     # steps' worth of launches, after that the host enqueues at the pace the device retires them -- whenever the device is the slower side
     # that figure tends to the device's time per step, whatever the host needs.
     idle = []
-    for _ in range(8):          # (every rank runs the same eight steps: their collectives match)
+    for _ in range(8 if args.full else 0):          # (every rank runs the same eight steps: their collectives match)
         torch.cuda.synchronize()
         ti = time.perf_counter()
         timed_step()
         idle.append(time.perf_counter() - ti)
     torch.cuda.synchronize()
     host_idle_ms = sorted(idle)[len(idle) // 2] * 1e3 if idle else None
-    if world > 1:
+    if world > 1 and host_idle_ms is not None:
         ti_all = torch.tensor([host_idle_ms], device=dev, dtype=torch.float64)
         dist.all_reduce(ti_all, op=dist.ReduceOp.MAX)          # the slowest rank's host
         host_idle_ms = float(ti_all)
     # sustained clocks: the timed region is a burst of `steps` x ~15 ms from a cool chip; the same step for a few seconds more, timed over its
     # tail (the driver line carries both figures). N = 1 only: no collective may differ between ranks' loop counts.
     sustained = None
-    if world == 1 and args.sustain_steps > 0:
+    if args.full and world == 1 and args.sustain_steps > 0:
         k_sus = args.sustain_steps
         for _ in range(k_sus // 3):
             timed_step()
@@ -825,7 +865,7 @@ def main():
     #  (2) with the production 3-stream schedule: the interval includes time shared with other streams -> `insitu`
     prof = prof_insitu = None
     dt_events = None
-    if not args.no_roofline:          # every rank runs the passes (the steps contain collectives); rank 0 records events
+    if args.full and not args.no_roofline:          # every rank runs the passes (the steps contain collectives); rank 0 records events
         was = model.overlap_streams
         model.overlap_streams = False
         one_step()
@@ -858,7 +898,7 @@ def main():
     assert torch.isfinite(losses).all(), f"non-finite losses {losses}"
     # the same step in fp32 parity mode (the reference's arithmetic precision), a secondary figure: N = 1 only, after everything else
     fp32_mode = bf16x3_mode = None
-    if world == 1 and args.dtype == "bf16" and not args.no_roofline and not args.graph:
+    if args.full and world == 1 and args.dtype == "bf16" and not args.no_roofline and not args.graph:
         model.compute_dtype = torch.float32
         one_step()
         torch.cuda.synchronize()
@@ -926,7 +966,7 @@ def main():
             # host-synchronous collectives it includes them). Until round 5 this field was the timed region's wall time per step, which includes waiting -- queue
             # back-pressure then, the replay's deliberate run-ahead bound (a sleeping poll, engine.ReplayedStep) now: that figure tends to the
             # DEVICE's time per step whenever the device is the slower side and is kept as host_wall_ms_per_step_timed_region.
-            "host_enqueue_ms_per_step": round(host_idle_ms if host_idle_ms is not None else host_ms, 3),
+            "host_enqueue_ms_per_step": (round(host_idle_ms, 3) if host_idle_ms is not None else None),          # --full only
             "host_enqueue_ms_from_idle_device": (round(host_idle_ms, 3) if host_idle_ms is not None else None),
             "host_wall_ms_per_step_timed_region": round(host_ms, 3),      # max over ranks; includes the waits described above
             "host_cpu_ms_per_step_by_thread": [{"thread": n, "ms": v} for v, n in cpu_threads if v > 0.05],
@@ -1042,7 +1082,7 @@ def main():
             out["fp32_mode"] = fp32_mode
         if bf16x3_mode is not None:
             out["bf16x3_mode"] = bf16x3_mode
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             # bounded: the oracle runs in a child process with a wall-clock limit (never part of the timed region)
             import subprocess
             code = ("import sys, json; sys.argv=['bench.py']; sys.path.insert(0, %r); import bench; "
