@@ -361,6 +361,15 @@ int unit_wsddn_mil(const float* streams, int ld, int ccol0, int dcol0, int K, co
 int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
                       const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, void* stream);
 int unit_sum_losses(const float* losses, int n, float* out, void* stream);
+/* PCL loss (weak detector TYPE "PCL"; building block -- the model does not call it yet): PCLFunction
+ * modeling/roi_heads/pcl_loss.py:6-61 as applied per image at weak_detector_fast_rcnn.py:233-238 -> *loss = sum_b loss_b / B and, with dy,
+ * dy[:, dcol0 : dcol0+K+1] = gscale * d(sum_b loss_b)/d(logits) (the reference's backward ignores grad_output: gscale 1 reproduces it).
+ * Images in fixed slots of S rows (valid[row] >= 0); per row labels (0..K, K = background), cls_weights, gt_assign (-1 or a cluster); per
+ * image n_pc[b] <= ldc clusters at b*ldc + j with pc_count, pc_img_cls_weights, pc_probs (compute_pcl_loss_inputs :488-507). logits and
+ * dy have B*S rows (dy's invalid rows get 0); ld >= col0+K+1, ldd >= dcol0+K+1, K < 96. acc: as for unit_softmax_ce. */
+int unit_pcl_loss(const float* logits, int ld, int col0, int K, const int* valid, int S, int B, const int* labels, const float* cls_weights,
+                  const int* gt_assign, const int* pc_count, const float* pc_img_cls_weights, const float* pc_probs, const int* n_pc,
+                  int ldc, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0, unsigned long long* acc, void* stream);
 /* sampling permutations (d2 `subsample_labels` -> torch.randperm; call sites rpn.py:41, roi_heads.py:563): keys [B][n] = hash of
  * (seed, *counter_dev, stream_id, b, i) as positive finite floats; `unit_sort_desc_stable` of them yields the permutation.
  * The device-resident counter is advanced by unit_counter_bump (graph-replay safe). */

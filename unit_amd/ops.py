@@ -1493,6 +1493,26 @@ def oicr_targets(src, col0, mode, k, rois5, valid, s, b, multihot, fg_thresh=0.5
     return labels, weights
 
 
+def pcl_loss(logits, col0, k, valid, s, b, labels, cls_weights, gt_assign, pc_count, pc_img_cls_weights, pc_probs, n_pc, dy=None, dcol0=0,
+             gscale=1.0, loss_out=None):
+    """PCL loss of one refinement stream (include/unit_hip.h: unit_pcl_loss): images in fixed slots of `s` rows (logits, valid, labels,
+    cls_weights, gt_assign, dy: b * s rows), clusters in [b, ldc] tables (pc_count int32, pc_img_cls_weights / pc_probs fp32), n_pc int32 [b].
+    Returns the loss [1]; dy gets the logits gradient in columns [dcol0, dcol0 + k + 1). A building block: the model does not call it yet."""
+    r, ld = logits.shape
+    rows = b * s
+    if r != rows or any(t.numel() != rows for t in (valid, labels, cls_weights, gt_assign)) or (dy is not None and dy.shape[0] != rows):
+        raise ValueError("pcl_loss: logits, valid, labels, cls_weights, gt_assign and dy need b * s rows")
+    ldc = pc_count.shape[1] if pc_count.dim() == 2 else -1
+    if any(t.dim() != 2 or tuple(t.shape) != (b, ldc) for t in (pc_count, pc_img_cls_weights, pc_probs)) or n_pc.numel() != b:
+        raise ValueError("pcl_loss: cluster tables must be [b, ldc] and n_pc [b]")
+    loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=logits.device)
+    check(lib().unit_pcl_loss(_p(logits), ld, col0, k, _p(valid), s, b, _p(labels), _p(cls_weights), _p(gt_assign), _p(pc_count),
+                              _p(pc_img_cls_weights), _p(pc_probs), _p(n_pc), ldc, float(gscale), _p(loss), _p(dy),
+                              dt(dy.dtype) if dy is not None else 0, dy.shape[1] if dy is not None else 0, dcol0, _p(_loss_acc(logits.device)),
+                              _s()), "pcl_loss")
+    return loss
+
+
 # ------------------------------------------------------------------------------------------------ a14 / a15
 def embedding_similarity(emb, novel_rows, base_rows):
     """fast_rcnn.py:376-382: E[novel] @ E[base]^T (row index lists are device int32 tensors)"""
