@@ -60,10 +60,11 @@ int unit_conv2d_fwd(const void* x, const void* w, void* y, const float* bias, co
                     int in_dtype, int out_dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int OH,
                     int OW, int ldy, int oy_mul, int OHf, int OWf, int relu, int tile_cfg, void* stream);
 /* large-tile variant (256x256x64, 8 waves, LDS-DMA operand staging) for the big-M layers; bf16 inputs, C % 64 == 0.
- * variant: 0 = default (= 8); 8 = four phases per k-tile, half-tile staging under a counted vmcnt, fragment reads inside the
- * MFMA sections (csrc/conv_igemm256p8.hip); 7 = 8 without the reads-in-MFMA step; 9 = 8 on 224-row tiles; 10 = 224 or 256
+ * variant: 0 = 8, resolved first (nothing in the environment or the build changes what 0 means); 8 = four phases per k-tile, half-tile
+ * staging under a counted vmcnt, fragment reads inside the MFMA sections (csrc/conv_igemm256p8.hip); 7 = 8 without the reads-in-MFMA step; 9 = 8 on 224-row tiles; 10 = 224 or 256
  * rows, whichever needs fewer rounds x rows; 4 = two-stage loop (csrc/conv_igemm256.hip), 1 / 2 / 3 / 5 / 6 = its ping-pong,
- * 4 x 32-k, 224-row, auto-row and shared-input-super-tile (3x3 s1 p1 on 7x7 maps) forms: identical results bit for bit.
+ * 4 x 32-k, 224-row, auto-row and shared-input-super-tile (3x3 s1 p1 on 7x7 maps; any other shape is refused) forms: identical results
+ * bit for bit. Any other number runs as 4.
  * 8 (and 0) on a 3x3 stride-1 pad-1 conv over a small map (the Res5 heads' conv2 and its dgrad on 7x7) cut the output into tiles of
  * ONE output position x 256 images and skip the filter taps that read only zero padding there (18 % of the k-tiles); 12 = 8 without that
  * (same results bit for bit).
@@ -72,7 +73,7 @@ int unit_conv2d_fwd(const void* x, const void* w, void* y, const float* bias, co
 int unit_conv2d_fwd_big(const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref,
                         int out_dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy,
                         int oy_mul, int OHf, int OWf, int relu, int variant, void* stream);
-/* unit_conv2d_fwd_big (variant 0 = default, 8 or 11; stride 1, plain output layout, bf16 in / out) with an extended epilogue -- any of:
+/* unit_conv2d_fwd_big (variant 0 = 8, or 11; stride 1, plain output layout, bf16 in / out) with an extended epilogue -- any of:
  *   relu_bits    out: one bit per output element, (stored value) > 0, unit_relu_bits_bytes(M, ldy) bytes, ldy % 64 == 0. Layout = the
  *                     epilogue's own order (one 16-byte store per lane and 128-row x 64-channel wave tile): 16-byte word
  *                     [(m / 128) * (ldy / 64) + n / 64][lane], lane = (m % 8) * 8 + (n % 64) / 8, bit ((m % 128) / 8) * 8 + n % 8;

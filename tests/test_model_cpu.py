@@ -176,6 +176,114 @@ def test_loader_consumer_tile_choice_is_host_arithmetic():
     assert ops.MID_TILE_POLICY(torch.bfloat16, 4 * 150 * 250, 256, 64, 576) < 100
 
 
+def _step_conv_layers():
+    """(m, k, c, r*s*c) of every conv of the step, forward and dgrad: the C4 backbone on four 600 x 1000 images (R50 and R101 have the same
+    layer shapes; the stem's 8-channel input keeps it on the generic kernel), the RPN head, the Res5 heads on 1024 and 2048 RoIs"""
+    out = []
+
+    def add(m, cin, cout, r):          # forward, and the dgrad as a conv of the gradient map with the transposed weights
+        for q in ((m, cout, cin, r * r * cin), (m, cin, cout, r * r * cout)):
+            if q not in out:
+                out.append(q)
+
+    def stage(m_in, m_out, cin, mid, cout):
+        add(m_out, cin, mid, 1); add(m_out, cin, cout, 1)          # first block: conv1 and the shortcut (stride in the 1x1)
+        add(m_out, mid, mid, 3); add(m_out, mid, cout, 1)
+        add(m_out, cout, mid, 1)                                   # later blocks' conv1
+
+    out.append((4 * 300 * 500, 64, 8, 7 * 7 * 8))                  # stem
+    m2, m3, m4 = 4 * 150 * 250, 4 * 75 * 125, 4 * 38 * 63
+    stage(m2, m2, 64, 64, 256); stage(m2, m3, 256, 128, 512); stage(m3, m4, 512, 256, 1024)
+    add(m4, 1024, 1024, 3); add(m4, 1024, 15, 1); add(m4, 1024, 60, 1)          # RPN head
+    for rois in (1024, 2048):
+        stage(rois * 196, rois * 49, 1024, 512, 2048)
+    return out
+
+
+# (big, mid) per layer of _step_conv_layers(), columns: bf16 output with ldy = K rounded up to 4 | fp32 output | bf16 output with ldy % 8 == 4 |
+# pair launch | pair launch with ldy % 8 == 4. Recorded by running BIG_TILE_POLICY / MID_TILE_POLICY and the fallbacks of conv2d / conv2d_pair
+# as they stood before select_conv_kernel existed (no switch set) on the same list.
+_STEP_CONV_KERNELS = {
+    (600000, 64, 8, 392): ((0, -1), (0, -1), (0, -1), (0, -1), (0, -1)),
+    (150000, 64, 64, 64): ((0, 2), (0, 2), (0, 2), (0, 2), (0, 2)),
+    (150000, 256, 64, 64): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (150000, 64, 256, 256): ((0, 2), (0, 2), (0, 2), (0, 2), (0, 2)),
+    (150000, 64, 64, 576): ((0, 2), (0, 2), (0, 2), (0, 2), (0, 2)),
+    (37500, 128, 256, 256): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (37500, 256, 128, 128): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (37500, 512, 256, 256): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (37500, 256, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (37500, 128, 128, 1152): ((0, 152), (0, 0), (0, 0), (0, 152), (0, 0)),
+    (37500, 512, 128, 128): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (37500, 128, 512, 512): ((0, 152), (0, 0), (0, 0), (0, 152), (0, 0)),
+    (9576, 256, 512, 512): ((0, 152), (0, 1), (0, 1), (0, 152), (0, 1)),
+    (9576, 512, 256, 256): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (9576, 1024, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (9576, 512, 1024, 1024): ((0, 154), (0, 0), (0, 0), (0, 154), (0, 0)),
+    (9576, 256, 256, 2304): ((0, 152), (0, 1), (0, 1), (0, 152), (0, 1)),
+    (9576, 1024, 256, 256): ((0, 0), (0, 0), (0, 0), (0, 0), (0, 0)),
+    (9576, 256, 1024, 1024): ((0, 152), (0, 1), (0, 1), (0, 152), (0, 1)),
+    (9576, 1024, 1024, 9216): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (9576, 15, 1024, 1024): ((0, -1), (0, -1), (0, -1), (0, -1), (0, -1)),
+    (9576, 1024, 15, 15): ((0, -1), (0, -1), (0, -1), (0, -1), (0, -1)),
+    (9576, 60, 1024, 1024): ((0, -1), (0, -1), (0, -1), (0, -1), (0, -1)),
+    (9576, 1024, 60, 60): ((0, -1), (0, -1), (0, -1), (0, -1), (0, -1)),
+    (50176, 512, 1024, 1024): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 1024, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 2048, 1024, 1024): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 1024, 2048, 2048): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 512, 512, 4608): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 2048, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (50176, 512, 2048, 2048): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 512, 1024, 1024): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 1024, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 2048, 1024, 1024): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 1024, 2048, 2048): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 512, 512, 4608): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 2048, 512, 512): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+    (100352, 512, 2048, 2048): ((1, -1), (1, -1), (1, -1), (1, -1), (0, 0)),
+}
+
+
+def test_select_conv_kernel_on_the_step_layers():
+    """ops.select_conv_kernel, the one place that decides which conv kernel a launch gets, chooses for every forward / dgrad layer of the R50 /
+    R101 step (4 x 600 x 1000) and of the Res5 heads (1024 and 2048 RoIs) what the three copies of the selection it replaced chose: the
+    literal table above, including fp32 outputs and rows that are not a multiple of 16 bytes (no loader / consumer kernel: the 4-wave
+    tile instead) and pair launches (no 256x256 kernel for such rows)."""
+    import torch
+    from unit_amd import ops
+    bf, f32 = torch.bfloat16, torch.float32
+    layers = _step_conv_layers()
+    assert set(layers) == set(_STEP_CONV_KERNELS) and len(layers) == len(_STEP_CONV_KERNELS)
+    for (m, k, c, kg) in layers:
+        ld = (k + 3) // 4 * 4
+        ld4 = ld if ld % 8 else ld + 4
+        got = (ops.select_conv_kernel(bf, m, k, c, kg, bf, ld), ops.select_conv_kernel(bf, m, k, c, kg, f32, ld),
+               ops.select_conv_kernel(bf, m, k, c, kg, bf, ld4), ops.select_conv_kernel(bf, m, k, c, kg, bf, ld, pair=True),
+               ops.select_conv_kernel(bf, m, k, c, kg, bf, ld4, pair=True))
+        assert tuple((int(b), t) for b, t in got) == _STEP_CONV_KERNELS[(m, k, c, kg)], (m, k, c, kg, got)
+    # fp32 inputs (compute_dtype fp32): the register-staged kernel, alone or in a pair
+    assert ops.select_conv_kernel(f32, 9576, 256, 1024, 1024, f32, 256) == (False, -1)
+    assert ops.select_conv_kernel(f32, 9576, 256, 1024, 1024, f32, 256, pair=True) == (False, -1)
+    # a policy that asks for a form the caller cannot run gets the 4-wave tile: the loader / consumer kernel for an fp32 output, the
+    # two-workgroups-per-CU form or tile 3 in a pair launch
+    old = ops.MID_TILE_POLICY
+    try:
+        ops.MID_TILE_POLICY = lambda dtype, m, k, c, kgemm, allow_lc=True: 152
+        assert ops.select_conv_kernel(bf, 9576, 256, 1024, 1024, f32, 256) == (False, 1)
+        assert ops.select_conv_kernel(bf, 9576, 256, 1024, 1024, bf, 256, pair=True) == (False, 152)
+        ops.MID_TILE_POLICY = lambda dtype, m, k, c, kgemm, allow_lc=True: 2152
+        assert ops.select_conv_kernel(bf, 9576, 256, 1024, 1024, bf, 256) == (False, 2152)
+        assert ops.select_conv_kernel(bf, 9576, 256, 1024, 1024, bf, 256, pair=True) == (False, 1)
+        ops.MID_TILE_POLICY = lambda dtype, m, k, c, kgemm, allow_lc=True: 3
+        assert ops.select_conv_kernel(bf, 150000, 64, 256, 256, bf, 64, pair=True) == (False, 2)
+    finally:
+        ops.MID_TILE_POLICY = old
+    # the explicit tile_cfg codes keep their meaning
+    assert {c: v for c, (kind, v) in ops.TILE_CFG.items() if kind == "big"} == {5: 0, 6: 1, 11: 2, 12: 3, 13: 4, 14: 6, 15: 7, 16: 8, 17: 9, 18: 10, 21: 11, 22: 12}
+    assert {c: v for c, (kind, v) in ops.TILE_CFG.items() if kind == "mid"} == {7: 0, 8: 1, 9: 2, 10: 3, 19: 4, 20: 5}
+
+
 def test_wgrad_group_plan_is_host_arithmetic():
     """unit_conv2d_wgrad_group_plan (tile kind and split count of every layer of a grouped weight-gradient launch) runs on the host:
     Res5-sized layers get 256x256 tiles and 3 slabs, a res4 gradient bucket 2, the RPN's 3x3 conv 3; 128-channel layers and a lone

@@ -1,6 +1,6 @@
 """Round 5: the epilogue diet of the 256x256 conv kernel (conv_epilogue.h: packed conversion / ReLU / bit forms, straight-line passes for the hot
 switch combinations) on the Res5 launches as the step issues them. Prints time per launch and a hash of every output so that two builds
-(UNIT_HIP_LIB=unit_amd/_build/noslim/libunit_hip.so = -DUNIT_EPI_SLIM=0) can be compared bit for bit.  python tools/epi_r5_bench.py"""
+(UNIT_HIP_LIB=<another build of the library>) can be compared bit for bit.  python tools/epi_r5_bench.py"""
 import hashlib
 import sys
 

@@ -115,14 +115,11 @@ struct EpiExtra {
 #define EPI_STAMP(i) do { } while (0)
 #endif
 // the epilogue's global accesses: a residual / mask segment is read once, an output segment is written once and read by a LATER kernel.
-// UNIT_EPI_NT: 2 (default) = the residual / mask loads are non-temporal, so that they do not push the operand tiles (weights, the pixel
-// rows the other channel tiles of the XCD are about to read) out of the 4 MB L2 -- FETCH_SIZE of a 512 -> 2048 launch is 3x its operands;
-// 1 = the stores too, 3 = the stores only, 0 = none. Same values in every form. Measured (profiles/r03_exp_epilogue_nontemporal.txt): with
-// loads AND stores the Res5 / RPN launches are 2-7 % faster in isolation (512 -> 2048 + residual 173 -> 161 us) but the step is not (the
-// consumers of the outputs then miss the Infinity Cache); loads only: step 16.40 -> 16.30 ms over five alternating runs.
-#ifndef UNIT_EPI_NT
-#define UNIT_EPI_NT 2
-#endif
+// The residual / mask loads are non-temporal, so that they do not push the operand tiles (weights, the pixel rows the other channel
+// tiles of the XCD are about to read) out of the 4 MB L2 -- FETCH_SIZE of a 512 -> 2048 launch is 3x its operands; the stores are plain.
+// Measured (profiles/r03_exp_epilogue_nontemporal.txt): with loads AND stores non-temporal the Res5 / RPN launches are 2-7 % faster in
+// isolation (512 -> 2048 + residual 173 -> 161 us) but the step is not (the consumers of the outputs then miss the Infinity Cache);
+// loads only: step 16.40 -> 16.30 ms over five alternating runs.
 // diagnostic builds only (tools/epi_issue.sh): bit 0 = the residual / mask loads come from registers instead of memory, bit 1 = the output
 // stores are issued only for a value that never occurs -- what is left is the epilogue's INSTRUCTION time (LDS round trip + VALU).
 #ifndef UNIT_EPI_DBG
@@ -135,62 +132,40 @@ __device__ __forceinline__ bf16x8 epi_load8(const bf16_t* q) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) v[j] = (bf16_t)(float)(((uintptr_t)q >> (4 + j)) & 3);
   return v;
-#elif UNIT_EPI_NT == 1 || UNIT_EPI_NT == 2
-  return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const epi_i32x4*>(q)));
 #else
-  return *reinterpret_cast<const bf16x8*>(q);
+  return __builtin_bit_cast(bf16x8, __builtin_nontemporal_load(reinterpret_cast<const epi_i32x4*>(q)));
 #endif
 }
 __device__ __forceinline__ void epi_store8(bf16_t* q, bf16x8 v) {
 #if UNIT_EPI_DBG & 2
   if (__builtin_bit_cast(epi_i32x4, v)[0] == 0x7fc17fc3) *reinterpret_cast<bf16x8*>(q) = v;
-#elif UNIT_EPI_NT == 1 || UNIT_EPI_NT == 3
-  __builtin_nontemporal_store(__builtin_bit_cast(epi_i32x4, v), reinterpret_cast<epi_i32x4*>(q));
 #else
   *reinterpret_cast<bf16x8*>(q) = v;
 #endif
 }
 
 // Instruction diet of a pass (round 4: the epilogue is bound by its ~150-200 instructions per 8-row pass, not by memory --
-// profiles/r04_exp_epilogue_issue.txt). UNIT_EPI_SLIM=0 restores the plain C forms (identical values; A/B and bit-identity tests).
-#ifndef UNIT_EPI_SLIM
-#define UNIT_EPI_SLIM 1
-#endif
+// profiles/r04_exp_epilogue_issue.txt): the forms below replace the plain C ones (fmaxf, select on a bit, per-element bf16 conversion)
+// with identical values.
 // max(x, 0) as ONE v_max_f32: fmaxf() compiles to a canonicalising v_max_f32 x, x in front of it (quiets a signalling NaN, nothing else)
 __device__ __forceinline__ float epi_relu(float x) {
-#if UNIT_EPI_SLIM
   float r;
   asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
   return r;
-#else
-  return fmaxf(x, 0.f);
-#endif
 }
 // bit ? x : +0 as bit-field extract + and (v_bfe_i32 gives 0 / -1) instead of and + compare + (VCC wait) + select
 __device__ __forceinline__ float epi_keep_if_bit(float x, unsigned bits, int j) {
-#if UNIT_EPI_SLIM
   return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, x) & (unsigned)__builtin_amdgcn_sbfe((int)bits, j, 1));
-#else
-  return ((bits >> j) & 1u) ? x : 0.f;
-#endif
-}
-// one bit per element of eight packed bf16 values, (value > 0). (A packed-integer form -- positive int16 per half word -- was tried in
-// round 4: hipcc folded its short-vector max / min into two compares for the first word only, wrong bits, caught by
-// test_conv_fused_pool_and_relu_bits; spelled out in 32-bit integer ops it needs more instructions than the eight compares + selects here.)
-__device__ __forceinline__ unsigned epi_positive_bits(bf16x8 o) {
-  unsigned bits = 0;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) bits |= ((float)o[j] > 0.f ? 1u : 0u) << j;
-  return bits;
 }
 
-// Packed forms of a pass's tail (round 5; UNIT_EPI_SLIM): the eight outputs of a lane live as four dwords of two bf16 each.
+// Packed forms of a pass's tail (round 5): the eight outputs of a lane live as four dwords of two bf16 each.
 //   epi_cvt_pk   : two fp32 -> one dword, ONE v_cvt_pk_bf16_f32 (the C conversion of a single value costs one each plus a v_perm per pair)
 //   epi_relu_pk  : max(x, 0) of both halves as signed 16-bit integers (a bf16 is negative iff its int16 is; -0 -> +0). Rounding commutes
 //                  with max(., 0), so relu-after-rounding stores the same bits as rounding-after-relu. (A positive NaN stays a NaN where
 //                  v_max_f32 would have returned 0: a diverged model, and the loss is NaN either way.)
 //   epi_positive_bits_pk : (value > 0) of the eight halves = (int16 > 0): clamp to [0, 1] per half, then fold the four dwords into a byte.
-// Spelled in inline assembly: hipcc's short-vector min / max folding produced wrong bits in round 4 (see epi_positive_bits above).
+// Spelled in inline assembly: written with short vectors in round 4, hipcc folded the max / min into two compares for the first word only
+// (wrong bits, caught by test_conv_fused_pool_and_relu_bits).
 __device__ __forceinline__ unsigned epi_cvt_pk(float a, float b) {
   unsigned r;
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -363,7 +338,7 @@ __device__ __forceinline__ void epilogue_rows_bf16_blocks(Put put_block, char* s
       }
       float v[8] = {t2[0][0], t2[0][1], t2[1][0], t2[1][1], t2[2][0], t2[2][1], t2[3][0], t2[3][1]};
       // max(., 0) commutes with the rounding: where nothing sits between them it runs on the packed result (4 instructions instead of 8)
-      const bool relu_packed = UNIT_EPI_SLIM && !SPL && do_relu && !has_mk && !has_mb;
+      const bool relu_packed = !SPL && do_relu && !has_mk && !has_mb;
       if (do_relu && !relu_packed) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = epi_relu(v[j]);
@@ -379,7 +354,6 @@ __device__ __forceinline__ void epilogue_rows_bf16_blocks(Put put_block, char* s
           for (int j = 0; j < 8; ++j) v[j] = epi_keep_if_bit(v[j], mbits, j);
         }
       }
-#if UNIT_EPI_SLIM
       u32x4 ow;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
@@ -387,18 +361,9 @@ __device__ __forceinline__ void epilogue_rows_bf16_blocks(Put put_block, char* s
         if (relu_packed) ow[i] = epi_relu_pk(ow[i]);
       }
       const bf16x8 o = __builtin_bit_cast(bf16x8, ow);
-#else
-      bf16x8 o;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (bf16_t)v[j];
-#endif
       if constexpr (EX) {
         if (has_rb && cur.ok[h]) {
-#if UNIT_EPI_SLIM
           unsigned bits = epi_positive_bits_pk(ow, do_relu);      // of the stored (rounded) value, as a mask_ref read would see it
-#else
-          unsigned bits = epi_positive_bits(o);
-#endif
           rw[(b * E::NP + h) >> 2] |= bits << (((b * E::NP + h) & 3) * 8);
         }
         if (has_pp && cur.ok[h]) {
@@ -409,26 +374,15 @@ __device__ __forceinline__ void epilogue_rows_bf16_blocks(Put put_block, char* s
 #pragma unroll
             for (int j = 0; j < 8; ++j) run[j] = 0.f;
           }
-#if UNIT_EPI_SLIM
 #pragma unroll
           for (int i = 0; i < 4; ++i) { run[2 * i] += epi_lo(ow[i]); run[2 * i + 1] += epi_hi(ow[i]); }
-#else
-#pragma unroll
-          for (int j = 0; j < 8; ++j) run[j] += (float)o[j];
-#endif
         }
         if (has_y && cur.ok[h]) epi_store8(Y + cur.off[h], o);
       } else if constexpr (SPL) {
-#if UNIT_EPI_SLIM
         u32x4 ow2;
 #pragma unroll
         for (int i = 0; i < 4; ++i) ow2[i] = epi_cvt_pk(v[2 * i] - epi_lo(ow[i]), v[2 * i + 1] - epi_hi(ow[i]));
         const bf16x8 o2 = __builtin_bit_cast(bf16x8, ow2);
-#else
-        bf16x8 o2;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o2[j] = (bf16_t)(v[j] - (float)o[j]);
-#endif
         if (cur.ok[h]) { epi_store8(Y + cur.off[h], o); epi_store8(Y + cur.off[h] + p.ldy, o2); }
       } else {
         if (cur.ok[h]) epi_store8(Y + cur.off[h], o);
@@ -475,14 +429,12 @@ __device__ __forceinline__ void epilogue_rows_bf16_impl(const f32x4 (&acc)[FA][F
 template <int FA, int FB, bool EX, bool PM, bool SPL, int... FLS, typename Args>
 __device__ __forceinline__ void epilogue_rows_bf16_dispatch(const f32x4 (&acc)[FA][FB], char* scr, float* pool, int m_w, int n_w, const Args& p, int lane,
                                                             const PmRows* rows = nullptr, unsigned long long* stamp = nullptr) {
-#if UNIT_EPI_SLIM
   int fl = SPL ? -2 : epi_flags<EX>(p);          // (split outputs: the straight-line forms measured 2 % SLOWER over the bf16x3 step, 40.15 -> 40.85-41.26 ms: dynamic form)
   if (!PM && m_w + FB * 16 <= p.M && n_w + FA * 16 <= p.K && n_w + FA * 16 <= p.ldy) fl |= EPI_FULL;
   bool done = false;
   if constexpr (!SPL)
     (void)((fl == FLS ? (epilogue_rows_bf16_impl<FA, FB, EX, PM, SPL, FLS>(acc, scr, pool, m_w, n_w, p, lane, rows, stamp), done = true) : false) || ...);
   if (done) return;
-#endif
   epilogue_rows_bf16_impl<FA, FB, EX, PM, SPL, -1>(acc, scr, pool, m_w, n_w, p, lane, rows, stamp);
 }
 

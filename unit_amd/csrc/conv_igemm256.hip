@@ -10,9 +10,6 @@
 #include "conv_igemm256.h"
 #include "conv_igemm128.h"
 #include "conv_pair.h"
-#ifndef UNIT_P8M_DEFAULT
-#define UNIT_P8M_DEFAULT 0
-#endif
 #include "conv_epilogue.h"
 
 // diagnostic builds only (tools/exp256.sh): 1 = no operand DMA after the first k-tile (MFMA + LDS-read bound of the loop),
@@ -628,9 +625,6 @@ static void build_position_classes(Conv256Args& a) {
   for (int i = 0; i < n; ++i) a.pm_cls[i] = cls[i].c;
 }
 
-// which MFMA shape variant 0 means for the p8 schedule (compile-time: no process state; callers A/B through the variant argument)
-int unit_conv256_use_m32() { return UNIT_P8M_DEFAULT; }
-
 // Same contract as unit_conv2d_fwd (include/unit_hip.h) restricted to bf16 inputs and C % 64 == 0.
 extern "C" int unit_conv2d_fwd_big(const void* x, const void* w, void* y, const float* bias, const void* residual,
                                    const void* mask_ref, int out_dtype, int N, int H, int W, int C, int K, int R, int S, int stride,
@@ -662,61 +656,44 @@ int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias,
   { int rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * 2); if (rc != UNIT_OK) return rc; }
   if (K == 0 || (a.M == 0 && !a.second.on)) return UNIT_OK;
   hipStream_t st = (hipStream_t)stream;
+  if (variant == 0) variant = 8;          // the production kernel; everything below decodes an explicit variant
   if (a.second.on) {          // pair launch: the phase-interleaved kernel on row-major 256-row tiles
-    UNIT_CHECK_ARG(out_dtype == UNIT_BF16 && (ldy & 7) == 0 && (variant == 0 || variant == 8 || variant == 12), "conv_big: pair launches: bf16 output, ldy % 8 == 0, variant 0 / 8 / 12");
+    UNIT_CHECK_ARG(out_dtype == UNIT_BF16 && (ldy & 7) == 0 && (variant == 8 || variant == 12), "conv_big: pair launches: bf16 output, ldy % 8 == 0, variant 0 / 8 / 12");
     return unit_conv256_p8_launch(a, out_dtype, true, false, st);
   }
-  // variant 0 / 4: one barrier per k-tile, 256-row tiles; 3: 224-row tiles; 5: 224 or 256 rows, whichever needs fewer
-  // rounds x rows (isolated launches gain 6-7 % on the Res5 shapes: 50 176 = 224 * 224 pixels; inside the multi-stream step
-  // the other streams already fill the partial last round and the 7 % extra operand feed of the smaller tile costs 0.8 %);
-  // 1: ping-pong wave groups; 2: four 32-k stages
-  // 6 (and 0 with UNIT_NO_HALO=0 when the shape allows it): 3x3 s1 p1 on 7x7 maps with the input super-tile shared by the nine taps
-  {
-    static int no_halo = -1;
-    if (no_halo < 0) { const char* e = getenv("UNIT_NO_HALO"); no_halo = e ? atoi(e) : 1; }   // default: the p8 kernel below is faster
+  // 224 or 256 rows per tile, whichever needs fewer rounds x rows (variants 5 and 10; isolated launches gain 5-7 % on the Res5 shapes:
+  // 50 176 = 224 * 224 pixels; inside the multi-stream step the other streams already fill the partial last round and the 7 % extra
+  // operand feed of the smaller tile costs 0.8 %, 19.4 vs 19.7 ms)
+  auto fewer_with_224 = [&] {
+    long n_tiles = cdiv(K, 256);
+    long c256 = (long)cdiv((long)cdiv(a.M, 256) * n_tiles, 256) * 256, c224 = (long)cdiv((long)cdiv(a.M, 224) * n_tiles, 256) * 224;
+    return c224 < c256;
+  };
+  // 6: 3x3 s1 p1 on 7x7 maps with the input super-tile shared by the nine taps (the p8 kernel is faster)
+  if (variant == 6) {
     bool halo_ok = out_dtype == UNIT_BF16 && (ldy & 7) == 0 && R == 3 && S == 3 && stride == 1 && pad == 1 && H == 7 && W == 7 &&
                    OH == 7 && OW == 7;
-    if (variant == 6 && !halo_ok) { unit_set_error("conv_big: variant 6 needs a bf16-out 3x3 s1 p1 conv on 7x7 maps"); return UNIT_ERR_UNSUPPORTED; }
-    if (halo_ok && (variant == 6 || (variant == 0 && !no_halo))) return launch256_halo7(a, st);
+    if (!halo_ok) { unit_set_error("conv_big: variant 6 needs a bf16-out 3x3 s1 p1 conv on 7x7 maps"); return UNIT_ERR_UNSUPPORTED; }
+    return launch256_halo7(a, st);
   }
-  // 7 / 8 (8 = default for variant 0; UNIT_P8=0 falls back to the two-stage kernels below, =1 selects 7): four phases per k-tile,
-  // half-tile staging under a counted vmcnt; 8 also issues the fragment reads inside the MFMA sections (conv_igemm256p8.hip)
-  {
-    static int p8 = -1;
-    if (p8 < 0) { const char* e = getenv("UNIT_P8"); p8 = e ? atoi(e) : 2; }
-    // 9: variant 8 on 224-row tiles; 10 (and 0 with UNIT_P8_ROWS=0): 224 or 256 rows, whichever needs fewer rounds x rows
-    // (+5 % per isolated launch on the Res5 shapes)
-    static int p8rows = -1;
-    if (p8rows < 0) { const char* e = getenv("UNIT_P8_ROWS"); p8rows = e ? atoi(e) : 256; }   // in the multi-stream step 256 rows win (19.4 vs 19.7 ms): the other streams fill the partial round
-    bool auto_rows = variant == 10 || (variant == 0 && p8 == 2 && p8rows == 0);
-    bool r224 = variant == 9 || (variant == 0 && p8 == 2 && p8rows == 224);
-    if (auto_rows) {
-      long n_tiles = cdiv(K, 256);
-      long c256 = (long)cdiv((long)cdiv(a.M, 256) * n_tiles, 256) * 256, c224 = (long)cdiv((long)cdiv(a.M, 224) * n_tiles, 256) * 224;
-      r224 = c224 < c256;
-      // (not where the position-class tiles apply: they need 256 rows and gain more)
-      if (variant == 0 && R == 3 && S == 3 && stride == 1 && pad == 1 && OH == H && OW == W && H * W <= 4096) r224 = false;
-    }
-    // 11 (and 0 when UNIT_P8M_DEFAULT is 1): the variant-8 schedule on v_mfma_f32_32x32x16_bf16 (conv_igemm256p8m.hip)
-    if (variant == 11 || (variant == 0 && p8 == 2 && !r224 && unit_conv256_use_m32())) return unit_conv256_p8m_launch(a, out_dtype, st);
-    // 12: variant 8 with row-major tiles even where position-major tiles apply (A/B and bit-identity tests)
-    if (variant == 12) return unit_conv256_p8_launch(a, out_dtype, true, false, st);
-    if (variant >= 7 && variant <= 10 || (variant == 0 && p8)) {
-      bool rm = variant >= 8 || (variant == 0 && p8 == 2);
-      // position-class tiles (Conv256Args::pm_ncls): 3x3 s1 p1 conv on a small map, plain bf16 output, when skipping the all-padding
-      // taps saves more k-tiles than padding every class to whole tiles costs
-      if (rm && !r224 && (variant == 0 || variant == 8) && out_dtype == UNIT_BF16 && (ldy & 7) == 0 && R == 3 && S == 3 && stride == 1 &&
-          pad == 1 && OH == H && OW == W && oy_mul == 1 && OHf == OH && OWf == OW && H * W <= 4096 && (size_t)N * H * W * ldy * 2 < 0xFFFFFFF0ull)
-        build_position_classes(a);
-      return unit_conv256_p8_launch(a, out_dtype, rm, r224, st);
-    }
+  // 11: the variant-8 schedule on v_mfma_f32_32x32x16_bf16 (conv_igemm256p8m.hip)
+  if (variant == 11) return unit_conv256_p8m_launch(a, out_dtype, st);
+  // 12: variant 8 with row-major tiles even where position-major tiles apply (A/B and bit-identity tests)
+  if (variant == 12) return unit_conv256_p8_launch(a, out_dtype, true, false, st);
+  // 7 / 8: four phases per k-tile, half-tile staging under a counted vmcnt; 8 also issues the fragment reads inside the MFMA sections
+  // (conv_igemm256p8.hip). 9: variant 8 on 224-row tiles; 10: 224 or 256 rows per launch
+  if (variant >= 7 && variant <= 10) {
+    bool r224 = variant == 9 || (variant == 10 && fewer_with_224());
+    // position-class tiles (Conv256Args::pm_ncls): 3x3 s1 p1 conv on a small map, plain bf16 output, when skipping the all-padding
+    // taps saves more k-tiles than padding every class to whole tiles costs
+    if (variant == 8 && out_dtype == UNIT_BF16 && (ldy & 7) == 0 && R == 3 && S == 3 && stride == 1 &&
+        pad == 1 && OH == H && OW == W && oy_mul == 1 && OHf == OH && OWf == OW && H * W <= 4096 && (size_t)N * H * W * ldy * 2 < 0xFFFFFFF0ull)
+      build_position_classes(a);
+    return unit_conv256_p8_launch(a, out_dtype, variant >= 8, r224, st);
   }
-  bool rows224 = variant == 3;
-  if (variant == 5) {
-    long n_tiles = cdiv(K, 256);
-    long c256 = cdiv((long)cdiv(a.M, 256) * n_tiles, 256) * 256, c224 = cdiv((long)cdiv(a.M, 224) * n_tiles, 256) * 224;
-    rows224 = c224 < c256;
-  }
+  // the two-stage kernels. 4 (and any other number): one barrier per k-tile, 256-row tiles; 3: 224-row tiles; 5: 224 or 256 rows per launch;
+  // 1: ping-pong wave groups; 2: four 32-k stages
+  bool rows224 = variant == 3 || (variant == 5 && fewer_with_224());
   if (out_dtype == UNIT_BF16) {
     if (variant == 2) return launch256_k32<bf16_t>(a, st);
     if (variant == 1) return launch256<bf16_t, true, 8>(a, st);
@@ -869,7 +846,7 @@ extern "C" int unit_conv2d_fwd_big_ex(const void* x, const void* w, void* y, con
   set_div_magics(a);
   a.ex = EpiExtra{relu_bits, mask_bits, pool_partial, pool_rows}; a.ex_on = 1;
   if (a.M == 0 || K == 0) return UNIT_OK;
-  if (variant == 11 || (variant == 0 && unit_conv256_use_m32())) return unit_conv256_p8m_launch(a, UNIT_BF16, (hipStream_t)stream);
+  if (variant == 11) return unit_conv256_p8m_launch(a, UNIT_BF16, (hipStream_t)stream);
   return unit_conv256_p8_launch(a, UNIT_BF16, true, false, (hipStream_t)stream);
 }
 

@@ -27,18 +27,6 @@
 //        t+1 by either group comes after the barrier that ends that interval.
 // Same swizzle / k order / accumulation order / epilogue as conv_igemm256.hip: results are bit-identical to it.
 #include "conv_igemm256.h"
-#ifndef UNIT_P8_X_AUX
-#define UNIT_P8_X_AUX 0       // cache policy of the LDS-DMA loads (buffer instruction aux bits; 2 = nt): pixel rows / weights (tools/exp_wait.sh)
-#endif
-#ifndef UNIT_P8_W_AUX
-#define UNIT_P8_W_AUX 0
-#endif
-#ifndef UNIT_P8_RD_PER
-#define UNIT_P8_RD_PER 1        // fragment reads per MFMA gap inside the MFMA sections of phases 1 and 3 (tools/exp_wait.sh)
-#endif
-#ifndef UNIT_P8_FINE_WAIT
-#define UNIT_P8_FINE_WAIT 0      // 1: one counted vmcnt wait per half-tile instead of one per k-tile / step (tools/exp_wait.sh: measured 1-8 % slower)
-#endif
 #include "conv_epilogue.h"
 
 // diagnostic builds only (tools/exp_p8.sh): 1 = no LDS-DMA inside the loop, 2 = MFMAs replaced by one VALU add per fragment,
@@ -233,9 +221,9 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
       }
       if (dual && st_cb >= p.cb_split) {      // (scalar branch) the row of x2: same pixel, ratio2 times the pitch; the 16-B chunk swizzle term stays
         unsigned o2 = (x_off0[q * 2 + j] - sw16) * (unsigned)p.ratio2 + sw16 + (unsigned)((st_cb - p.cb_split) * BK) * 2u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX2, (lds_void*)(base + (j * 8 + wid) * 1024), 16, ok ? o2 : OOB, 0, 0, UNIT_P8_X_AUX);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX2, (lds_void*)(base + (j * 8 + wid) * 1024), 16, ok ? o2 : OOB, 0, 0, 0);
       } else
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void*)(base + (j * 8 + wid) * 1024), 16, ok ? x_off0[q * 2 + j] + st_kx : OOB, 0, 0, UNIT_P8_X_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void*)(base + (j * 8 + wid) * 1024), 16, ok ? x_off0[q * 2 + j] + st_kx : OOB, 0, 0, 0);
     }
   };
   auto stage_w = [&](int q, int d) {
@@ -243,7 +231,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       unsigned o = w_off[q * 2 + j];
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void*)(base + (j * 8 + wid) * 1024), 16, o == OOB ? OOB : o + st_kw, 0, 0, UNIT_P8_W_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_void*)(base + (j * 8 + wid) * 1024), 16, o == OOB ? OOB : o + st_kw, 0, 0, 0);
     }
   };
 
@@ -352,9 +340,9 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
     //        W1(t): M(t, 0) -> L(t, 3): 3.
     //   RAW: vmcnt in L(t, 2) of both groups (two half-tiles younger than k-tile t+1 may stay in flight); first read of
     //        k-tile t+1 in M(t, 3), which for either group starts after the barrier that ends the later group's L(t, 2).
-    //        (UNIT_P8_FINE_WAIT=1: every half-tile waited for separately, with the four half-tiles issued after it still in flight, one
-    //        phase before the MFMA section that reads it -- X1(t+1) then has four phases to land instead of two. Measured 1-8 % SLOWER
+    //        (One counted wait per half-tile instead -- X1(t+1) then has four phases to land instead of two -- measured 1-8 % SLOWER
     //        on every Res5 / RPN shape, profiles/r03_exp_fine_vmcnt.txt: the loop is not waiting for that half-tile.)
+    constexpr int RD_PER = 1;          // fragment reads per MFMA gap inside the MFMA sections of phases 1 and 3
     i32x4 fxb[B1][2];
     auto read_xb = [&](const char* half) {
 #pragma unroll
@@ -403,47 +391,28 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
       // phase 0
       if (n1) stage_x(1, d ^ 1);
       st_advance();
-#if UNIT_P8_FINE_WAIT
-      if (n1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // X1(t) landed (read in M(t, 1)); X0, W0, W1, X1 of t+1 younger
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       P8_BAR();
       P8_MM(0, 0, fw0, fx, 4, 4, 1, read_w(buf + SW1, fw1));
       P8_BAR();
       // phase 1
       if (n2) stage_x(0, d);
       P8_BAR();
-      P8_MM(0, 1, fw1, fx, 4, 2 * B1, UNIT_P8_RD_PER, read_xb(buf + SX1));
+      P8_MM(0, 1, fw1, fx, 4, 2 * B1, RD_PER, read_xb(buf + SX1));
       P8_BAR();
       // phase 2
-#if UNIT_P8_FINE_WAIT
-      if (n2) {
-        stage_w(0, d);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // X0, W0 of t+1 landed (read in M(t, 3)); W1, X1 of t+1, X0, W0 of t+2 younger
-      } else if (n1) {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             // W1, X1 of t+1 younger
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-#else
       if (n2) {
         stage_w(0, d);
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-#endif
       P8_BAR();
       P8_MM(1, 0, fw0, fxb, B1, 0, 1, (void)0);
       P8_BAR();
       // phase 3 (after the last k-tile the reads fetch stale, in-bounds LDS that nobody uses)
       if (n2) stage_w(1, d);
-#if UNIT_P8_FINE_WAIT
-      if (n2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // W1(t+1) landed (read in M(t+1, 0)); X1(t+1), X0, W0, W1 of t+2 younger
-      else if (n1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // X1(t+1) younger
-#endif
       P8_BAR();
-      P8_MM(1, 1, fw1, fxb, B1, 12, UNIT_P8_RD_PER, read_w(bnx + SW0, fw0); read_x(bnx + SX0));
+      P8_MM(1, 1, fw1, fxb, B1, 12, RD_PER, read_w(bnx + SW0, fw0); read_x(bnx + SX0));
       P8_BAR();
     }
     if (grp == 0) P8_BAR();

@@ -151,11 +151,7 @@ __device__ __forceinline__ void wgrad128_ring_tile(const Wgrad256Args& p, int ti
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       int k = k0 + wk * 64 + a * 16 + fq * 4;
-#if UNIT_SLAB_NT
-      __builtin_nontemporal_store(acc[a][b], reinterpret_cast<f32x4*>(out + (size_t)n * p.Kgemm + k));     // read back once, by a later kernel
-#else
       *reinterpret_cast<f32x4*>(out + (size_t)n * p.Kgemm + k) = acc[a][b];
-#endif
     }
   }
 }
@@ -219,17 +215,13 @@ int unit_wgrad128_group_launch(const WgradGroupArgs& g, int slots_per_xcd, hipSt
 }
 
 int unit_wgrad128_ring_launch(const Wgrad256Args& a, hipStream_t st) {
-  // UNIT_WG128_NS=3: three stages (48 KB of LDS, three workgroups per CU) instead of four (64 KB, two per CU)
-  static int ns = -1;
-  if (ns < 0) { const char* e = getenv("UNIT_WG128_NS"); ns = e ? atoi(e) : 4; }
+  // four stages: 64 KB of LDS, two workgroups per CU
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)conv_wgrad128_ring_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 32 * 256);
-    (void)hipFuncSetAttribute((const void*)conv_wgrad128_ring_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 3 * 2 * 32 * 256);
     attr_set = true;
   }
-  if (ns == 3) conv_wgrad128_ring_kernel<3><<<a.tiles_k * a.tiles_n * a.splits, 256, 3 * 2 * 32 * 256, st>>>(a);
-  else conv_wgrad128_ring_kernel<4><<<a.tiles_k * a.tiles_n * a.splits, 256, 4 * 2 * 32 * 256, st>>>(a);
+  conv_wgrad128_ring_kernel<4><<<a.tiles_k * a.tiles_n * a.splits, 256, 4 * 2 * 32 * 256, st>>>(a);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

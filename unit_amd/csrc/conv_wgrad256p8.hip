@@ -19,19 +19,8 @@
 //   phase 3: stage D1(t+2) ; quadrant (1,1) = fxb x fd1 || read X0(t+1) -> fx, D0(t+1) -> fd0
 // WAR / RAW distances are those of conv_igemm256p8.hip (reads retired by lgkmcnt(0) before the barrier that ends their
 // MFMA section; a slot is restaged >= 2 phases after its last read; first read of step t+1 one phase after both groups'
-// vmcnt wait; UNIT_P8_FINE_WAIT as there). Same m permutation inside a fragment and same accumulation order as conv_wgrad256.hip: bit-identical slabs.
+// vmcnt wait). Same m permutation inside a fragment and same accumulation order as conv_wgrad256.hip: bit-identical slabs.
 #include "conv_wgrad256.h"
-#ifndef UNIT_W8_AUX
-#define UNIT_W8_AUX 0          // cache policy of the LDS-DMA loads (2 = nt; tools/exp_wait.sh)
-#endif
-#ifndef UNIT_W8_PER0
-#define UNIT_W8_PER0 1          // transposing fragment reads per MFMA gap in phases 0 / 1 / 3 (tools/exp_wait.sh)
-#define UNIT_W8_PER1 1
-#define UNIT_W8_PER3 2
-#endif
-#ifndef UNIT_P8_FINE_WAIT
-#define UNIT_P8_FINE_WAIT 0      // 1: one counted vmcnt wait per half-tile instead of one per k-tile / step (tools/exp_wait.sh: measured 1-8 % slower)
-#endif
 
 // one 256 x 256 tile of dW over the pixels [split * mps, +mps) of a contraction of Meff rows. vo (Wgrad256Args::valid_only): the rows are
 // (image, valid output position of the tile's filter tap): positions = rows v_oh0.. of the map, columns v_ow0.. of v_cw, nv per image.
@@ -138,7 +127,7 @@ __device__ __forceinline__ void wgrad256_p8_tile(const Wgrad256Args& p, int tile
         ok = ok && (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
         xoff = ((unsigned)n * (unsigned)(p.H * p.W * p.x_pitch) + (unsigned)((ih * p.W + iw) * p.x_pitch) + xcol[q]) * 2u;
       }
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void_w*)(base + (j * 8 + wid) * 1024), 16, ok ? xoff : OOB, 0, 0, UNIT_W8_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsX, (lds_void_w*)(base + (j * 8 + wid) * 1024), 16, ok ? xoff : OOB, 0, 0, 0);
     }
   };
   auto stage_d = [&](int q, int d, int mstep) {
@@ -156,7 +145,7 @@ __device__ __forceinline__ void wgrad256_p8_tile(const Wgrad256Args& p, int tile
     for (int j = 0; j < 2; ++j) {
       int m = mstep + s_row[j];
       unsigned doff = ((unsigned)(vo ? xn[j] * p.OHW + tv[j] : m) * (unsigned)p.ldy + dcol[q]) * 2u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsD, (lds_void_w*)(base + (j * 8 + wid) * 1024), 16, m < m_end ? doff : OOB, 0, 0, UNIT_W8_AUX);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsD, (lds_void_w*)(base + (j * 8 + wid) * 1024), 16, m < m_end ? doff : OOB, 0, 0, 0);
     }
   };
 
@@ -225,6 +214,7 @@ __device__ __forceinline__ void wgrad256_p8_tile(const Wgrad256Args& p, int tile
     if ((NR) > 0) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                   \
   } while (0)
 
+  constexpr int PER0 = 1, PER1 = 1, PER3 = 2;          // transposing fragment reads per MFMA gap in phases 0 / 1 / 3
   const int nsteps = (m_end - m_begin + MS - 1) / MS;
   if (nsteps > 0) {
     int mst = m_begin;
@@ -253,47 +243,28 @@ __device__ __forceinline__ void wgrad256_p8_tile(const Wgrad256Args& p, int tile
       // phase 0
       if (n1) stage_x(1, d ^ 1, mst);
       mst += MS; x_advance();
-#if UNIT_P8_FINE_WAIT
-      if (n1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");      // X1(t) landed (read in M(t, 1)); X0, D0, D1, X1 of t+1 younger
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
       W8_BAR();
-      W8_MM(0, 0, fx, fd0, 8, UNIT_W8_PER0, W8_RD(W8_READ_D(buf + SD1, fd1)));
+      W8_MM(0, 0, fx, fd0, 8, PER0, W8_RD(W8_READ_D(buf + SD1, fd1)));
       W8_BAR();
       // phase 1
       if (n2) stage_x(0, d, mst);
       W8_BAR();
-      W8_MM(0, 1, fx, fd1, 16, UNIT_W8_PER1, W8_RD(W8_READ_X(buf + SX1, fxb)));
+      W8_MM(0, 1, fx, fd1, 16, PER1, W8_RD(W8_READ_X(buf + SX1, fxb)));
       W8_BAR();
       // phase 2
-#if UNIT_P8_FINE_WAIT
-      if (n2) {
-        stage_d(0, d, mst);
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");             // X0, D0 of t+1 landed (read in M(t, 3)); D1, X1 of t+1, X0, D0 of t+2 younger
-      } else if (n1) {
-        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");             // D1, X1 of t+1 younger
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-#else
       if (n2) {
         stage_d(0, d, mst);
         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-#endif
       W8_BAR();
       W8_MM(1, 0, fxb, fd0, 0, 0, (void)0);
       W8_BAR();
       // phase 3 (after the last step the reads fetch stale, in-bounds LDS that nobody uses)
       if (n2) stage_d(1, d, mst);
-#if UNIT_P8_FINE_WAIT
-      if (n2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");       // D1(t+1) landed (read in M(t+1, 0)); X1(t+1), X0, D0, D1 of t+2 younger
-      else if (n1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // X1(t+1) younger
-#endif
       W8_BAR();
-      W8_MM(1, 1, fxb, fd1, 24, UNIT_W8_PER3, W8_RD(W8_READ_D(bnx + SD0, fd0); W8_READ_X(bnx + SX0, fx)));
+      W8_MM(1, 1, fxb, fd1, 24, PER3, W8_RD(W8_READ_D(bnx + SD0, fd0); W8_READ_X(bnx + SX0, fx)));
       W8_BAR();
     }
     if (grp == 0) W8_BAR();
@@ -323,11 +294,7 @@ __device__ __forceinline__ void wgrad256_p8_tile(const Wgrad256Args& p, int tile
 #pragma unroll
     for (int a = 0; a < 8; ++a) {
       int k = k0 + wk * 128 + a * 16 + fq * 4;
-#if UNIT_SLAB_NT
-      __builtin_nontemporal_store(acc[a][b], reinterpret_cast<f32x4*>(out + (size_t)n * p.Kgemm + k));     // read back once, by a later kernel
-#else
       *reinterpret_cast<f32x4*>(out + (size_t)n * p.Kgemm + k) = acc[a][b];
-#endif
     }
   }
 #endif

@@ -192,18 +192,13 @@ def _big_tile_default(dtype, m, k, c, kgemm):
     return tiles >= 128
 
 
-_NO_MID = bool(int(__import__("os").environ.get("UNIT_NO_MID_TILE", "0")))   # A/B switch for tools/ and debugging
-
-
-_LC_TWO = bool(int(os.environ.get("UNIT_LC_TWO", "0")))      # A/B switch: 1 = the two-workgroups-per-CU form of the loader / consumer kernel where it won in isolation
-_NO_LC = bool(int(os.environ.get("UNIT_NO_LC", "0")))      # A/B switch: 1 = never the persistent loader / consumer conv kernel (csrc/conv_igemm_lc.hip)
-# 1 = the loader / consumer kernel's weights-direct form (csrc/conv_igemm_lc.hip WD: weight fragments from L2 straight into the consumers'
-# registers, only pixels through LDS); 0 (default) = both operands staged in LDS. Measured SLOWER in round 6 (profiles/r06_exp_weights_direct.txt:
-# res4 1x1 1024 -> 256 12.6 -> 14.0 us, 3x3 20.5 -> 24.2 us, step 15.12 -> 15.69 ms): the k-step is not waiting for the LDS port, it waits for
-# what one CU takes in from L2 (~29 B/clk, the guide's "rows shared by every workgroup" rate), and 64-byte fragment rows are a worse shape for
-# that path than the 128-byte rows of the LDS-DMA pieces. Kept as a bit-identical variant (tile codes + 8000) and as the evidence.
-_LC_WD = int(os.environ.get("UNIT_LC_WD", "0"))
-_MID96 = int(os.environ.get("UNIT_MID96", "0"))      # 0: off; 1: 96x128 tiles where tools/mid_sweep.py found them faster in isolation; 2: only the two-per-CU form
+def _four_wave_tile(m, k):
+    """the 4-wave LDS-DMA tile (csrc/conv_igemm128.hip) of an [m pixels] x [k channels] layer: 128x64 for 64-channel outputs, 128x128 when
+    that gives every CU a workgroup, 64x128 below that (tools/mid_sweep.py: res3, 293 tiles, 22.4 vs 26.2 us with 128x128; res4, 150 tiles,
+    27.5 vs 32.9 with 64x128)"""
+    if k <= 64:
+        return 2
+    return 0 if ((m + 127) // 128) * ((k + 127) // 128) >= 256 else 1
 
 
 def mid_tile_dims(mid):
@@ -242,40 +237,61 @@ def _mid_tile_default(dtype, m, k, c, kgemm, allow_lc=True):
     26.8 -> 18.9 us, tools/lc_sweep.py); short contractions (K = 256 -> 1024: four k-steps per tile) and the large res2 / res3 maps stay
     on the 4-wave tiles, which measured equal or better there.
     Measured on the backbone shapes (tools/microbench.py): 128x64 for 64-channel outputs, 128x128 when that tiling still
-    gives every CU a workgroup or two, 64x128 below that."""
-    if dtype != torch.bfloat16 or c % 64 != 0 or k < 64 or _NO_MID:
+    gives every CU a workgroup or two, 64x128 below that.
+    Forms that measured no gain inside the step and are reachable by explicit tile code only: two loader / consumer workgroups per CU
+    (+ 2000), weights fetched straight into registers (+ 8000), 96-row tiles (4 / 5) -- profiles/r03_exp_loader_consumer.txt,
+    profiles/r06_exp_weights_direct.txt, profiles/r02_exp_mid_sweep_96_row_tiles.txt."""
+    if dtype != torch.bfloat16 or c % 64 != 0 or k < 64:
         return -1
     if k <= 64:
         return 2
     tiles = ((m + 127) // 128) * ((k + 127) // 128)
-    # two loader / consumer workgroups per CU on a two-slot ring (code + 2000; off unless UNIT_LC_TWO=1): where every CU has two or more
-    # 80 x 128 tiles, one workgroup's epilogue runs beside the other's k-steps. Isolated (tools/lc_sweep.py two): res4 256 -> 1024
-    # 17.3 -> 16.0 us, res3 512 -> 128 14.4 -> 12.8, res3 3x3 21.9 -> 17.6 (with one tile per CU -- res4 -> 256 layers -- the three-slot
-    # one-per-CU form stays ahead, with two k-steps per tile -- res3 128 -> 512 -- the 4-wave kernel, the 1024-wide transition layer is a
-    # tie). In the step: 16.31 ms without vs 16.35 ms with it (three alternating runs each) -- not enabled.
-    t80 = ((m + 79) // 80) * ((k + 127) // 128)
-    lc = allow_lc and not _NO_LC
-    if lc and _LC_TWO and k % 8 == 0 and kgemm >= 256 and 384 <= t80 <= 1024 and not (kgemm >= 512 and k >= 1024):
-        return 2152
-    if lc and kgemm >= 512 and tiles <= 640 and k % 8 == 0:
-        return lc_tile_code(m, k, kgemm) + (8000 if _LC_WD else 0)
-    if _MID96:
-        # 96-row tiles (tools/mid_sweep.py, profiles/r02_exp_mid_sweep_96_row_tiles.txt): the res4 1x1 -> 256 layers become 100 x 2 = 200
-        # workgroups, one round with one workgroup per CU (14.9 vs 15.6 us; 3x3: 26.7 vs 27.9); between one and 2.5 rounds of 128x128
-        # tiles the 2-stage 96x128 form (two workgroups per CU) wins: res3 512 -> 128 12.7 vs 15.4 us, 3x3 19.6 vs 22.1, res4 256 -> 1024 16.6 vs 17.8
-        if tiles < 256:
-            return (4 if ((m + 95) // 96) * ((k + 127) // 128) <= 256 else 1) if _MID96 == 1 else 1
-        if tiles <= 640:
-            return 5
-        return 0
-    return 0 if tiles >= 256 else 1      # tools/mid_sweep.py: res3 (293 tiles) 22.4 vs 26.2 us with 128x128; res4 (150) 27.5 vs 32.9 with 64x128
+    if allow_lc and kgemm >= 512 and tiles <= 640 and k % 8 == 0:
+        return lc_tile_code(m, k, kgemm)
+    return _four_wave_tile(m, k)
 
 
 MID_TILE_POLICY = _mid_tile_default
 BIG_TILE_POLICY = _big_tile_default
-# 0: one barrier per k-tile, 256-row tiles; 1: ping-pong wave groups; 2: four 32-k stages; 3: 224-row tiles; 5: 224 or 256
-# rows per launch, whichever needs fewer rounds x rows (faster for isolated launches, see csrc/conv_igemm256.hip)
-BIG_TILE_VARIANT = int(__import__("os").environ.get("UNIT_BIG_VARIANT", "0"))
+
+
+def select_conv_kernel(dtype, m, k, c, kgemm, out_dtype, ldy, pair=False):
+    """the production kernel of a conv layer with m output pixels, k filters, c input channels and a contraction of kgemm = r * s * c:
+    (big, mid) -- big: the 256x256 kernel (unit_conv2d_fwd_big, variant 0); else mid >= 0: that tile of unit_conv2d_fwd_mid; else the
+    register-staged unit_conv2d_fwd. pair: for unit_conv2d_fwd_pair (m = the pixels of both problems), whose big kernel writes rows of
+    16-byte vectors and whose mid kernel has no instantiation of tile 3 and of the two-workgroups-per-CU loader / consumer forms."""
+    if BIG_TILE_POLICY(dtype, m, k, c, kgemm) and not (pair and ldy % 8):
+        return True, -1
+    lc_ok = out_dtype == torch.bfloat16 and ldy % 8 == 0        # the loader / consumer kernel writes bf16 rows of 16-byte vectors
+    mid = MID_TILE_POLICY(dtype, m, k, c, kgemm, allow_lc=lc_ok)
+    if (mid >= 100 and not lc_ok) or (pair and (2000 <= mid < 8000 or mid == 3)):
+        mid = _four_wave_tile(m, k)
+    return False, mid
+
+
+# explicit `tile_cfg` codes of conv2d (tests, tools/, profiles/ name them): code -> ("big", variant of unit_conv2d_fwd_big) or
+# ("mid", tile of unit_conv2d_fwd_mid). A code >= 100 is a loader / consumer tile code and goes to unit_conv2d_fwd_mid as it is;
+# any other code is the tile_cfg of unit_conv2d_fwd.
+TILE_CFG = {
+    5: ("big", 0),       # the production kernel (= 8)
+    6: ("big", 1),       # two-stage loop, ping-pong wave groups
+    7: ("mid", 0),       # 4-wave 128x128
+    8: ("mid", 1),       # 4-wave 64 pixels x 128 channels
+    9: ("mid", 2),       # 4-wave 128 x 64
+    10: ("mid", 3),      # 4-wave 128x128 with in-workgroup split-K
+    11: ("big", 2),      # two-stage loop, four 32-k stages
+    12: ("big", 3),      # two-stage loop, 224-row tiles
+    13: ("big", 4),      # two-stage loop, one barrier per k-tile
+    14: ("big", 6),      # shared input super-tile (3x3 s1 p1 on 7x7 maps)
+    15: ("big", 7),      # four phases per k-tile
+    16: ("big", 8),      # ... with the fragment reads inside the MFMA sections
+    17: ("big", 9),      # 8 on 224-row tiles
+    18: ("big", 10),     # 8 on 224 or 256 rows, whichever needs fewer rounds x rows
+    19: ("mid", 4),      # 4-wave 96 x 128, three LDS stages
+    20: ("mid", 5),      # 4-wave 96 x 128, two LDS stages
+    21: ("big", 11),     # the schedule of 8 on v_mfma_f32_32x32x16_bf16
+    22: ("big", 12),     # 8 without the position-class tiles
+}
 
 # side HIP stream for the weight-gradient kernels (set by the model when stream overlap is enabled; None = inline)
 WGRAD_STREAM = None
@@ -429,24 +445,6 @@ def conv_out_size(h, w, r, s, stride, pad):
 _POLICY_CACHE = {}
 
 
-_POLICY_SIG = {}
-
-
-def _policy_takes_allow_lc(fn):
-    """does this tile policy accept the `allow_lc` keyword? Looked at once per policy object (a TypeError raised INSIDE a policy must
-    surface, not be mistaken for the old five-argument signature)."""
-    r = _POLICY_SIG.get(fn)
-    if r is None:
-        import inspect
-        try:
-            ps = inspect.signature(fn).parameters
-            r = "allow_lc" in ps or any(q.kind is inspect.Parameter.VAR_KEYWORD for q in ps.values())
-        except (TypeError, ValueError):
-            r = True
-        _POLICY_SIG[fn] = r
-    return r
-
-
 def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=None, relu=False, out_dtype=None,
            out=None, ldy=None, scatter=None, tile_cfg=0):
     """x [N,H,W,C] NHWC ; w [k][r][s][C] (same dtype). Returns y [N,OH,OW,ldy] (or writes the strided scatter target).
@@ -473,30 +471,21 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
     if prof is not None:
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
+    big, mid, variant = False, -1, 0
     if tile_cfg == 0:          # the two policy functions cost ~5 us per call (the loader / consumer tile search): cached per shape
-        pkey = (x.dtype, n * oh * ow, k, c, r * s * c, out_dtype, ldy % 8, BIG_TILE_POLICY, MID_TILE_POLICY, _NO_LC, _MID96, _LC_TWO, _NO_MID)
+        pkey = (x.dtype, n * oh * ow, k, c, r * s * c, out_dtype, ldy % 8, BIG_TILE_POLICY, MID_TILE_POLICY)
         pol = _POLICY_CACHE.get(pkey)
-    else:
-        pkey = pol = None
-    big = tile_cfg in (5, 6, 11, 12, 13, 14, 15, 16, 17, 18, 21, 22) or (tile_cfg == 0 and (pol[0] if pol is not None else BIG_TILE_POLICY(x.dtype, n * oh * ow, k, c, r * s * c)))
-    mid = -1
-    if pol is not None:
-        mid = pol[1]
-    elif tile_cfg >= 100:          # persistent loader / consumer workgroups: 100 + 10 * (BM / 16) + BN / 64 (csrc/conv_igemm_lc.hip)
+        if pol is None:
+            pol = _POLICY_CACHE[pkey] = select_conv_kernel(x.dtype, n * oh * ow, k, c, r * s * c, out_dtype, ldy)
+        big, mid = pol
+    elif tile_cfg >= 100:
         mid = tile_cfg
-    elif tile_cfg in (7, 8, 9, 10, 19, 20):
-        mid = {19: 4, 20: 5}.get(tile_cfg, tile_cfg - 7)
-    elif tile_cfg == 0 and not big:
-        lc_ok = out_dtype == torch.bfloat16 and ldy % 8 == 0        # the loader / consumer kernel writes bf16 rows of 16-byte vectors
-        if _policy_takes_allow_lc(MID_TILE_POLICY):
-            mid = MID_TILE_POLICY(x.dtype, n * oh * ow, k, c, r * s * c, allow_lc=lc_ok)
-        else:                      # a user-supplied policy with the five-argument signature
-            mid = MID_TILE_POLICY(x.dtype, n * oh * ow, k, c, r * s * c)
-        if mid >= 100 and not lc_ok:          # ... that asked for the loader / consumer kernel anyway: the best 4-wave tile instead
-            tiles = ((n * oh * ow + 127) // 128) * ((k + 127) // 128)
-            mid = 2 if k <= 64 else (0 if tiles >= 256 else 1)
-    if pkey is not None and pol is None:
-        _POLICY_CACHE[pkey] = (big, mid)
+    elif tile_cfg in TILE_CFG:
+        kind, code = TILE_CFG[tile_cfg]
+        if kind == "big":
+            big, variant = True, code
+        else:
+            mid = code
     if mid >= 0:
         check(lib().unit_conv2d_fwd_mid(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
                                         n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), mid, _s()),
@@ -504,7 +493,7 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
     elif big:
         check(lib().unit_conv2d_fwd_big(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
                                         n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu),
-                                        BIG_TILE_VARIANT if tile_cfg == 0 else {5: 0, 6: 1, 11: 2, 12: 3, 13: 4, 14: 6, 15: 7, 16: 8, 17: 9, 18: 10, 21: 11, 22: 12}[tile_cfg], _s()),
+                                        variant, _s()),
               "unit_conv2d_fwd_big")
     else:
         check(lib().unit_conv2d_fwd(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(x.dtype), dt(out_dtype),
@@ -573,8 +562,6 @@ def conv2d_ex(x, w, k, r, s, pad=0, bias=None, residual=None, relu=False, mask_b
     the channel concatenation [x | x2] with w = [k][1][1][C + C2] (C2 a multiple of C)."""
     n, h, wd, c = x.shape
     c2 = 0
-    if variant == 0 and BIG_TILE_VARIANT in (8, 11):
-        variant = BIG_TILE_VARIANT
     if x2 is not None:
         c2 = x2.shape[3]
         assert r == 1 and s == 1 and pad == 0 and x2.shape[:3] == x.shape[:3] and c2 % c == 0 and x2.dtype == x.dtype and w.shape[-1] == c + c2
@@ -823,14 +810,7 @@ def conv2d_pair(xs, w, k, r, s, stride=1, pad=0, bias=None, residuals=None, mask
         assert segs in (2, 3) and w.shape[-1] == segs * c
         kernel, tile = (3 if segs == 3 else 4), X3_TILE_POLICY(m_tot, k, c, segs * r * s * c)
     else:
-        big = BIG_TILE_POLICY(x0.dtype, m_tot, k, c, r * s * c) and ldy % 8 == 0
-        mid = -1
-        if not big:
-            lc_ok = x0.dtype == torch.bfloat16 and ldy % 8 == 0
-            mid = MID_TILE_POLICY(x0.dtype, m_tot, k, c, r * s * c, allow_lc=lc_ok)
-            if 2000 <= mid < 8000 or mid == 3:          # forms without a pair instantiation: the plain 4-wave tile instead
-                tiles = ((m_tot + 127) // 128) * ((k + 127) // 128)
-                mid = 2 if k <= 64 else (0 if tiles >= 256 else 1)
+        big, mid = select_conv_kernel(x0.dtype, m_tot, k, c, r * s * c, x0.dtype, ldy, pair=True)
         kernel, tile = (2, 0) if big else ((1, mid) if mid >= 0 else (0, 0))
     g0, g1 = geo
     sec = ConvSecond()
@@ -858,9 +838,9 @@ def x3_tile_policy(m, k, c, kgemm_v):
     if k <= 64:
         return 2
     tiles = ((m + 127) // 128) * ((k + 127) // 128)
-    if not _NO_LC and kgemm_v >= 512 and tiles <= 640 and k % 8 == 0:
+    if kgemm_v >= 512 and tiles <= 640 and k % 8 == 0:
         return lc_tile_code(m, k, kgemm_v)
-    return 0 if tiles >= 256 else 1
+    return _four_wave_tile(m, k)
 
 
 X3_TILE_POLICY = x3_tile_policy
@@ -890,7 +870,7 @@ def conv2d_x3(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref
     segs = w.shape[-1] // c          # 3 = [Wh | Wh | Wl]; 2 = [Wh | Wl], the two-segment dgrad copy (weight_prep_x3 dgrad_segs)
     assert segs in (2, 3) and w.shape[-1] == segs * c, "conv2d_x3: w is a weight_prep_x3 copy"
     if tile is None:
-        pkey = ("x3", m, k, c, r * s, X3_TILE_POLICY, _NO_LC, segs)
+        pkey = ("x3", m, k, c, r * s, X3_TILE_POLICY, segs)
         tile = _POLICY_CACHE.get(pkey)
         if tile is None:
             tile = _POLICY_CACHE[pkey] = X3_TILE_POLICY(m, k, c, segs * r * s * c)
