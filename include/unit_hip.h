@@ -362,7 +362,7 @@ int unit_wsddn_mil(const float* streams, int ld, int ccol0, int dcol0, int K, co
 int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
                       const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, void* stream);
 int unit_sum_losses(const float* losses, int n, float* out, void* stream);
-/* PCL loss (weak detector TYPE "PCL"; building block -- the model does not call it yet): PCLFunction
+/* PCL loss (weak detector TYPE "PCL"; the model calls it after unit_pcl_targets): PCLFunction
  * modeling/roi_heads/pcl_loss.py:6-61 as applied per image at weak_detector_fast_rcnn.py:233-238 -> *loss = sum_b loss_b / B and, with dy,
  * dy[:, dcol0 : dcol0+K+1] = gscale * d(sum_b loss_b)/d(logits) (the reference's backward ignores grad_output: gscale 1 reproduces it).
  * Images in fixed slots of S rows (valid[row] >= 0); per row labels (0..K, K = background), cls_weights, gt_assign (-1 or a cluster); per
@@ -371,6 +371,25 @@ int unit_sum_losses(const float* losses, int n, float* out, void* stream);
 int unit_pcl_loss(const float* logits, int ld, int col0, int K, const int* valid, int S, int B, const int* labels, const float* cls_weights,
                   const int* gt_assign, const int* pc_count, const float* pc_img_cls_weights, const float* pc_probs, const int* n_pc,
                   int ldc, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0, unsigned long long* acc, void* stream);
+/* PCL targets: compute_pcl_loss_inputs weak_detector_fast_rcnn.py:476-507 (get_graph_centers :415-463: per image-level class the k-means of
+ * get_top_ranking_proposals :465-474, the IoU graph of the top-ranking rows, the greedy clustering, at most max_pc_num centres, removal;
+ * then Matcher([0.5]) of every row against the centres) for B images and a list of n_streams refinement streams in one launch, under the
+ * canonical tie rule of DESIGN.md section 8 (the reference under a stable argsort). Stream t reads its scores at src columns
+ * col0 + t*step (mode 0: K probabilities per row, e.g. unit_wsddn_mil's xr_out; mode 1: K+1 logits, softmax taken here, == unit_softmax_rows)
+ * and the next iteration's scores, which pc_probs averages, at nxt columns ncol0 + t*nstep (nmode as mode, K+1 columns); both clamped to
+ * [1e-9, 1 - 1e-9]. Images in fixed slots of S <= 2048 rows (valid[row] >= 0); multihot [B][K]. Outputs in unit_pcl_loss's layout, stream
+ * t at offset t*B*S (labels, cls_weights, gt_assign), t*B*ldc (pc_labels, pc_count, pc_img_cls_weights, pc_probs; slots >= n_pc: -1 / 0)
+ * and t*B (n_pc). ldc >= max_pc_num * (classes an image can carry): an image with more clusters than ldc is poisoned (NaN weights), as
+ * is one where the reference raises (no edge left in the graph: zero-area boxes). K < 96. The workspace is scratch (never read across
+ * calls); its query is NOT named unit_pcl_*: every unit_pcl_* prototype is a stream call (tests/test_pcl_cpu.py).
+ * unit_kmeans_draws: host only, the IEEE bits of the 7 doubles one KMeans(3, random_state=3) fit draws, constants of the kernel. */
+size_t unit_workspace_bytes_pcl_targets(int B, int S, int n_streams);
+int unit_kmeans_draws(unsigned long long* bits7);
+int unit_pcl_targets(const float* src, int ld, int col0, int mode, int step, const float* nxt, int ldn, int ncol0, int nmode, int nstep, int K,
+                     const float* rois5, const int* valid, int S, int B, int n_streams, const unsigned char* multihot, float fg_thresh,
+                     float bg_thresh, float graph_iou_thresh, int max_pc_num, int* labels, float* cls_weights, int* gt_assign, int* n_pc,
+                     int* pc_labels, int* pc_count, float* pc_img_cls_weights, float* pc_probs, int ldc, void* workspace,
+                     size_t workspace_bytes, void* stream);
 /* sampling permutations (d2 `subsample_labels` -> torch.randperm; call sites rpn.py:41, roi_heads.py:563): keys [B][n] = hash of
  * (seed, *counter_dev, stream_id, b, i) as positive finite floats; `unit_sort_desc_stable` of them yields the permutation.
  * The device-resident counter is advanced by unit_counter_bump (graph-replay safe). */

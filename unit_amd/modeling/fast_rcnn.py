@@ -1,7 +1,7 @@
 """Box predictors -- MI355X counterparts of
   * SupervisedDetectorOutputsBase      /root/reference/modeling/roi_heads/fast_rcnn.py:293-468
   * SupervisedDetectorOutputsFineTune  /root/reference/modeling/roi_heads/fast_rcnn.py:471-533
-  * WeakDetectorOutputsBase            /root/reference/modeling/roi_heads/weak_detector_fast_rcnn.py:39-408 (OICR type)
+  * WeakDetectorOutputsBase            /root/reference/modeling/roi_heads/weak_detector_fast_rcnn.py:39-519 (TYPE "OICR" and "PCL")
 Parameter names equal the reference's (`cls_score_delta`, `bbox_pred_delta`, `cls_score_ft`, `bbox_pred_ft`,
 `weak_detector_head.{classifier_stream,detection_stream,oicr_predictors.k}`, `embeddings.weight`).
 All Linear layers that share an input run as one fused GEMM (LinearGroup); the loss kernels emit loss + gradient."""
@@ -26,8 +26,12 @@ class WeakDetectorOutputsBase(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
         wd = cfg.MODEL.ROI_HEADS.FAST_RCNN.WEAK_DETECTOR
-        assert wd.TYPE == "OICR" and not wd.REGRESSION_BRANCH and not wd.OICR_REGRESSION_BRANCH, \
-            "only the OICR configuration shipped in the VOC/COCO C4 yaml files is on the hot path"
+        assert wd.TYPE in ("OICR", "PCL") and not wd.REGRESSION_BRANCH and not wd.OICR_REGRESSION_BRANCH, \
+            "WEAK_DETECTOR.TYPE is \"OICR\" or \"PCL\", without the regression branches (REGRESSION_BRANCH / OICR_REGRESSION_BRANCH)"
+        assert wd.TYPE != "PCL" or wd.NUM_KMEANS_CLUSTER == 3, \
+            "TYPE \"PCL\" needs NUM_KMEANS_CLUSTER == 3: the only k-means the device kernel restates (csrc/pcl.hip, tests/golden/pcl_kmeans.py)"
+        self.weak_detector_type = wd.TYPE
+        self.graph_iou_threshold, self.max_pc_num = wd.GRAPH_IOU_THRESHOLD, wd.MAX_PC_NUM
         self.num_classes = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         self.oicr_iter = wd.OICR_ITER
         self.fg_threshold, self.bg_threshold = wd.FG_THRESHOLD, wd.BG_THRESHOLD
@@ -66,6 +70,43 @@ class WeakDetectorOutputsBase(nn.Module):
                 lab, wts = ops.oicr_targets(lin, self.col_oicr[it - 1], 1, k, rois5, valid, rois_per_image, n_images, multihot,
                                             self.fg_threshold, self.bg_threshold)
             ops.softmax_ce(lin, self.col_oicr[it], k + 1, lab, weights=wts, dy=dy, dcol0=self.col_oicr[it], loss_out=loss_out[1 + it:2 + it])
+
+        def pcl(its, xr):
+            """TYPE "PCL" (:225-238): unit_pcl_targets for the consecutive iterations `its` in one launch, then unit_pcl_loss per stream.
+            PCLFunction.backward ignores grad_output, so the reference's refinement gradient carries neither the 1 / images of the
+            loss's mean nor any loss weight: gscale is 1 whatever the image count."""
+            cols = self.col_oicr
+            step = cols[1] - cols[0] if self.oicr_iter > 1 else 0
+            if any(cols[i + 1] - cols[i] != step for i in range(self.oicr_iter - 1)):       # (never with equal-width predictors)
+                for it in its[1:]:
+                    pcl([it], xr)
+                its = its[:1]
+            first = its[0]
+            src, col0, mode = (xr, 0, 0) if first == 0 else (lin, cols[first - 1], 1)
+            assert first > 0 or len(its) == 1
+            t = ops.pcl_targets(src, col0, mode, lin, cols[first], 1, k, rois5, valid, rois_per_image, n_images, multihot,
+                                ldc=self.max_pc_num * k, n_streams=len(its), step=step, nstep=step, fg_thresh=self.fg_threshold,
+                                bg_thresh=self.bg_threshold, graph_iou_thresh=self.graph_iou_threshold, max_pc_num=self.max_pc_num)
+            for j, it in enumerate(its):
+                ops.pcl_loss(lin, cols[it], k, valid, rois_per_image, n_images, t["labels"][j], t["cls_weights"][j], t["gt_assign"][j],
+                             t["pc_count"][j], t["pc_img_cls_weights"][j], t["pc_probs"][j], t["n_pc"][j], dy=dy, dcol0=cols[it], gscale=1.0,
+                             loss_out=loss_out[1 + it:2 + it])
+
+        if self.weak_detector_type == "PCL":
+            later = list(range(1, self.oicr_iter))
+            if side_stream is not None and later:
+                side_stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side_stream):
+                    pcl(later, None)
+            _, xr = ops.wsddn_mil(lin, self.col_cls, self.col_det, k, valid, rois_per_image, n_images, multihot, self.classifier_temp,
+                                  self.detector_temp, self.mil_multiplier, dy=dy, dyc0=self.col_cls, dyd0=self.col_det, loss_out=loss_out[0:1])
+            if self.oicr_iter > 0:
+                pcl([0], xr)
+            if side_stream is not None and later:
+                torch.cuda.current_stream().wait_stream(side_stream)
+            elif later:
+                pcl(later, None)
+            return dy
 
         if side_stream is not None and self.oicr_iter > 1:
             main = torch.cuda.current_stream()
@@ -111,7 +152,8 @@ class WeakDetectorOutputsBase(nn.Module):
         return [[lin[:, c:c + k + 1] for c in self.col_oicr], torch.zeros((lin.shape[0], 4 * k), device=lin.device)], None
 
     def losses(self, weak_predictions, weak_proposals, weak_targets):
-        """:189-255 -> {'loss_im_cls', 'loss_oicr_1..n'} (HIP kernels unit_wsddn_mil / unit_oicr_targets / unit_softmax_ce). With predictions
+        """:189-255 -> {'loss_im_cls', 'loss_oicr_1..n'} (HIP kernels unit_wsddn_mil / unit_oicr_targets / unit_softmax_ce; TYPE "PCL":
+        unit_pcl_targets / unit_pcl_loss, whose refinement gradient ignores the weight that arrives, as PCLFunction.backward does). With predictions
         that carry a graph (training-mode forward) the losses do too: one autograd node whose backward hands out the gradient the loss kernels
         emit, scaled by the weight that arrives. weak_predictions = forward()'s list, weak_proposals = list[Instances(proposal_boxes)],
         weak_targets = list[LongTensor]."""

@@ -496,6 +496,7 @@ class _WeakLossFn(torch.autograd.Function):
         dy = ctx.dy.clone()
         dy[:, wh.col_cls:wh.col_cls + k] *= g[0]
         dy[:, wh.col_det:wh.col_det + k] *= g[0]
-        for i, c in enumerate(wh.col_oicr):
-            dy[:, c:c + k + 1] *= g[1 + i]
+        if wh.weak_detector_type != "PCL":          # PCLFunction.backward (pcl_loss.py:40-61) ignores grad_output: under TYPE "PCL" the
+            for i, c in enumerate(wh.col_oicr):     # refinement columns keep the gradient the loss kernel emitted, whatever weight arrives
+                dy[:, c:c + k + 1] *= g[1 + i]
         return dy, None, None

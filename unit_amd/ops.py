@@ -1477,7 +1477,7 @@ def pcl_loss(logits, col0, k, valid, s, b, labels, cls_weights, gt_assign, pc_co
              gscale=1.0, loss_out=None):
     """PCL loss of one refinement stream (include/unit_hip.h: unit_pcl_loss): images in fixed slots of `s` rows (logits, valid, labels,
     cls_weights, gt_assign, dy: b * s rows), clusters in [b, ldc] tables (pc_count int32, pc_img_cls_weights / pc_probs fp32), n_pc int32 [b].
-    Returns the loss [1]; dy gets the logits gradient in columns [dcol0, dcol0 + k + 1). A building block: the model does not call it yet."""
+    Returns the loss [1]; dy gets the logits gradient in columns [dcol0, dcol0 + k + 1)."""
     r, ld = logits.shape
     rows = b * s
     if r != rows or any(t.numel() != rows for t in (valid, labels, cls_weights, gt_assign)) or (dy is not None and dy.shape[0] != rows):
@@ -1491,6 +1491,40 @@ def pcl_loss(logits, col0, k, valid, s, b, labels, cls_weights, gt_assign, pc_co
                               dt(dy.dtype) if dy is not None else 0, dy.shape[1] if dy is not None else 0, dcol0, _p(_loss_acc(logits.device)),
                               _s()), "pcl_loss")
     return loss
+
+
+def kmeans_draws():
+    """the 7 float64 draws of RandomState(3) that unit_pcl_targets carries as constants (host only)"""
+    import numpy as np
+    bits = (ctypes.c_ulonglong * 7)()
+    check(lib().unit_kmeans_draws(bits), "kmeans_draws")
+    return np.frombuffer(bytes(bits), dtype=np.float64).copy()
+
+
+def pcl_targets(src, col0, mode, nxt, ncol0, nmode, k, rois5, valid, s, b, multihot, ldc, n_streams=1, step=0, nstep=0, fg_thresh=0.5,
+                bg_thresh=0.1, graph_iou_thresh=0.4, max_pc_num=5):
+    """PCL targets of `n_streams` refinement streams (include/unit_hip.h: unit_pcl_targets) -> dict of unit_pcl_loss's inputs, every entry
+    with a leading stream axis: labels / cls_weights / gt_assign [n_streams, b * s], pc_labels / pc_count / pc_img_cls_weights / pc_probs
+    [n_streams, b, ldc], n_pc [n_streams, b]. Stream t reads src columns col0 + t * step and nxt columns ncol0 + t * nstep.
+    Nothing here is a stock torch operator: torch.empty only reserves memory (the step's pool under ReplayedStep)."""
+    dev, rows = src.device, b * s
+    if rois5.shape[0] != rows or valid.numel() != rows or src.shape[0] != rows or nxt.shape[0] != rows:
+        raise ValueError("pcl_targets: src, nxt, rois5 and valid need b * s rows")
+    if multihot.numel() != b * k:
+        raise ValueError("pcl_targets: multihot must be [b, k]")
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = dict(labels=i32(n_streams, rows), cls_weights=f32(n_streams, rows), gt_assign=i32(n_streams, rows), n_pc=i32(n_streams, b),
+               pc_labels=i32(n_streams, b, ldc), pc_count=i32(n_streams, b, ldc), pc_img_cls_weights=f32(n_streams, b, ldc),
+               pc_probs=f32(n_streams, b, ldc))
+    nb = lib().unit_workspace_bytes_pcl_targets(b, s, n_streams)
+    ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
+    check(lib().unit_pcl_targets(_p(src), src.shape[1], col0, mode, step, _p(nxt), nxt.shape[1], ncol0, nmode, nstep, k, _p(rois5), _p(valid),
+                                 s, b, n_streams, _p(multihot), float(fg_thresh), float(bg_thresh), float(graph_iou_thresh), int(max_pc_num),
+                                 _p(out["labels"]), _p(out["cls_weights"]), _p(out["gt_assign"]), _p(out["n_pc"]), _p(out["pc_labels"]),
+                                 _p(out["pc_count"]), _p(out["pc_img_cls_weights"]), _p(out["pc_probs"]), ldc, _p(ws), nb, _s()),
+          "pcl_targets")
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ a14 / a15
