@@ -209,6 +209,10 @@ int unit_conv2d_wgrad_group(const UnitWgradProblem* pr, int n, int in_dtype, voi
  * filter tap, split, first tile of the unit within its (layer [, tap], split)}. Units that contract over the same rows share an XCD's L2:
  * the tiles of one (layer, split), and for the in-map 3x3 form the filter taps that walk at the same pace (corner / edge / centre). */
 int unit_conv2d_wgrad_group_layout(const UnitWgradProblem* pr, int n, int* layout, int layout_rows, int* rows);
+/* Loop schedule of the 256x256 weight-gradient tile (csrc/conv_wgrad256p8.hip) that the next launch will run: 1 = fragment reads placed
+ * gap by gap and the staging offsets made once per 64-pixel step, 0 = the earlier schedule, kept for A/B runs and the equality tests.
+ * UNIT_WGRAD_LOOP=0/1 overrides the default and is read at every launch; every schedule writes the same slabs bit for bit. */
+int unit_wgrad256_loop(void);
 /* stream fork / join without host-side event objects: everything enqueued on `waiter` after this call waits for everything enqueued on
  * `signaller` before it (the reference reaches this through torch.cuda.Stream.wait_stream / Event; here the step forks ~100 weight-gradient
  * launches per step to a side stream: engine/defaults.py:279-284's backward has no such structure, it is the explicit plan's own). */
