@@ -333,8 +333,11 @@ extern "C" int unit_softmax_rows(const float* x, int ld, int ncls, float* y, int
   return UNIT_OK;
 }
 
-// fast_rcnn_inference_single_image, first half: decode (weights w), clip, score > thresh -> candidates in (roi, class)
-// row-major order, compacted. One workgroup per image. Also returns max coordinate over the candidates (batched_nms offset).
+// fast_rcnn_inference_single_image, first half: decode (weights w), drop non-finite RoIs, clip, score > thresh -> candidates in
+// (roi, class) row-major order, compacted. One workgroup per image. Also returns max coordinate over the candidates (batched_nms offset).
+// A RoI is dropped WHOLE when any of its K decoded boxes (before clipping) or any of its K+1 scores is non-finite (detectron2
+// fast_rcnn_inference_single_image: `valid_mask = isfinite(boxes).all(1) & isfinite(scores).all(1)`). More than `cap`
+// candidates: the first `cap` in (roi, class) order are kept.
 __device__ __forceinline__ int2 det_scan2(int2 v, int2* total, int2* lds) {
   int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
   int2 inc = v;
@@ -354,17 +357,45 @@ __device__ __forceinline__ int2 det_scan2(int2 v, int2* total, int2* lds) {
   return ex;
 }
 
+// Box2BoxTransform.apply_deltas for one (RoI, class); torch.clamp(max=) keeps a NaN dw / dh, so must the comparison here (fminf would not)
+__device__ __forceinline__ f32x4 det_decode(const float* __restrict__ dp, const float* __restrict__ pb, f32x4 w, float clampv) {
+  float bw = pb[2] - pb[0], bh = pb[3] - pb[1];
+  float cx = pb[0] + 0.5f * bw, cy = pb[1] + 0.5f * bh;
+  float dx = dp[0] / w[0], dy = dp[1] / w[1];
+  float dw = dp[2] / w[2], dh = dp[3] / w[3];
+  dw = dw > clampv ? clampv : dw; dh = dh > clampv ? clampv : dh;
+  float pcx = dx * bw + cx, pcy = dy * bh + cy;
+  float pw = expf(dw) * bw, ph = expf(dh) * bh;
+  return f32x4{pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
+}
+
+#define DET_MAX_RCAP (1 << 18)          // one validity bit per RoI in LDS: 32 KB
+
 __global__ void det_select_kernel(const float* __restrict__ probs, int ldp, const float* __restrict__ deltas, int ldd,
                                   const float* __restrict__ props, const int* __restrict__ pcount, int Rcap, int K, f32x4 w,
                                   float clampv, const float* __restrict__ image_hw, float thresh, int cap, float* __restrict__ cboxes,
                                   float* __restrict__ cscores, int* __restrict__ cclass, int* __restrict__ croi, int* __restrict__ ccount,
                                   float* __restrict__ cmax) {
+  extern __shared__ unsigned dropped[];          // [cdiv(Rcap, 32)] bit r: RoI r has a non-finite box or score
   __shared__ int2 lds[17];
   __shared__ float smax[16];
   int b = blockIdx.x;
   int R = min(pcount ? pcount[b] : Rcap, Rcap);
   float imh = image_hw[2 * b], imw = image_hw[2 * b + 1];
   int total = R * K;
+  for (int i = threadIdx.x; i < (R + 31) / 32; i += blockDim.x) dropped[i] = 0u;
+  __syncthreads();
+  // validity of every RoI: all K boxes before clipping, all K+1 scores (the thread of class 0 also looks at the background score)
+  for (int i = threadIdx.x; i < total; i += blockDim.x) {
+    int r = i / K, k = i - r * K;
+    size_t row = (size_t)b * Rcap + r;
+    float sc = probs[row * ldp + k];
+    f32x4 bx = det_decode(deltas + row * ldd + 4 * k, props + row * 4, w, clampv);
+    bool fin = isfinite(bx[0]) && isfinite(bx[1]) && isfinite(bx[2]) && isfinite(bx[3]) && isfinite(sc);
+    if (k == 0) fin = fin && isfinite(probs[row * ldp + K]);
+    if (!fin) atomicOr(&dropped[r >> 5], 1u << (r & 31));
+  }
+  __syncthreads();
   int chunk = (total + blockDim.x - 1) / blockDim.x;
   int i0 = threadIdx.x * chunk, i1 = min(total, i0 + chunk);
   int2 c = {0, 0};
@@ -376,25 +407,13 @@ __global__ void det_select_kernel(const float* __restrict__ probs, int ldp, cons
       int r = i / K, k = i - r * K;
       size_t row = (size_t)b * Rcap + r;
       float sc = probs[row * ldp + k];
-      const float* dp = deltas + row * ldd + 4 * k;
-      const float* pb = props + row * 4;
-      f32x4 bx;
-      {
-        float bw = pb[2] - pb[0], bh = pb[3] - pb[1];
-        float cx = pb[0] + 0.5f * bw, cy = pb[1] + 0.5f * bh;
-        float dx = dp[0] / w[0], dy = dp[1] / w[1];
-        float dw = fminf(dp[2] / w[2], clampv), dh = fminf(dp[3] / w[3], clampv);
-        float pcx = dx * bw + cx, pcy = dy * bh + cy;
-        float pw = expf(dw) * bw, ph = expf(dh) * bh;
-        bx = f32x4{pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
-      }
-      bool fin = isfinite(bx[0]) && isfinite(bx[1]) && isfinite(bx[2]) && isfinite(bx[3]) && isfinite(sc);
-      bx[0] = fminf(fmaxf(bx[0], 0.f), imw); bx[1] = fminf(fmaxf(bx[1], 0.f), imh);
-      bx[2] = fminf(fmaxf(bx[2], 0.f), imw); bx[3] = fminf(fmaxf(bx[3], 0.f), imh);
-      bool keep = fin && sc > thresh;
+      bool keep = !((dropped[r >> 5] >> (r & 31)) & 1u) && sc > thresh;
       if (pass == 0) { c.x += keep ? 1 : 0; }
       else if (keep) {
         if (ex.x < cap) {
+          f32x4 bx = det_decode(deltas + row * ldd + 4 * k, props + row * 4, w, clampv);
+          bx[0] = fminf(fmaxf(bx[0], 0.f), imw); bx[1] = fminf(fmaxf(bx[1], 0.f), imh);
+          bx[2] = fminf(fmaxf(bx[2], 0.f), imw); bx[3] = fminf(fmaxf(bx[3], 0.f), imh);
           size_t o = (size_t)b * cap + ex.x;
           *reinterpret_cast<f32x4*>(cboxes + 4 * o) = bx;
           cscores[o] = sc; cclass[o] = k; croi[o] = r;
@@ -414,10 +433,12 @@ extern "C" int unit_detection_candidates(const float* probs, int ldp, const floa
                                          int B, int Rcap, int K, const float* weights4, float scale_clamp, const float* image_hw_dev,
                                          float score_thresh, int cap, float* cand_boxes, float* cand_scores, int* cand_class, int* cand_roi,
                                          int* cand_count, float* cand_max, void* stream) {
+  UNIT_CHECK_ARG(Rcap >= 0 && Rcap <= DET_MAX_RCAP, "detection_candidates: at most 262144 RoIs per image");
   if (B == 0) return UNIT_OK;
   f32x4 w = {weights4[0], weights4[1], weights4[2], weights4[3]};
-  det_select_kernel<<<B, 1024, 0, (hipStream_t)stream>>>(probs, ldp, deltas, ldd, props, pcount, Rcap, K, w, scale_clamp, image_hw_dev,
-                                                        score_thresh, cap, cand_boxes, cand_scores, cand_class, cand_roi, cand_count, cand_max);
+  size_t lds_bytes = (size_t)cdiv(Rcap, 32) * sizeof(unsigned);
+  det_select_kernel<<<B, 1024, lds_bytes, (hipStream_t)stream>>>(probs, ldp, deltas, ldd, props, pcount, Rcap, K, w, scale_clamp, image_hw_dev,
+                                                                score_thresh, cap, cand_boxes, cand_scores, cand_class, cand_roi, cand_count, cand_max);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

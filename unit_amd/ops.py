@@ -1587,7 +1587,13 @@ def softmax_rows(x, ncls):
 
 def detections(probs, deltas, props, pcount, image_hw, weights, score_thresh, nms_thresh, topk, cand_cap=None):
     """fast_rcnn_inference for B images: probs [B*Rcap, K+1], deltas [B*Rcap, 4K], props [B,Rcap,4], pcount [B] (device)
-    -> (boxes [B,topk,4], scores [B,topk], classes [B,topk], roi_idx [B,topk], count [B])"""
+    -> (boxes [B,topk,4], scores [B,topk], classes [B,topk], roi_idx [B,topk], count [B]); rows past count[b] hold 0 / 0 / -1 / -1.
+    Non-finite predictions: a RoI is dropped WHOLE when any of its K decoded boxes (before clipping; a NaN dw / dh is not clamped away)
+    or any of its K+1 scores, background included, is non-finite -- detectron2's row filter in fast_rcnn_inference_single_image.
+    roi_idx counts the image's ORIGINAL proposal rows (gather_rows on similarity['seg'] needs those); the reference reports indices into
+    its filtered rows, which differ once a row was dropped.
+    Ties in score keep (RoI, class) order (stable sort). More than `cand_cap` candidates above the threshold (default min(Rcap * K,
+    65536)): the first cand_cap in (RoI, class) order go on to the sort and NMS, the rest are cut silently, whatever their scores."""
     b, rcap = props.shape[0], props.shape[1]
     k = deltas.shape[1] // 4
     dev = probs.device
