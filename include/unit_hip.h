@@ -478,6 +478,24 @@ int unit_gather_match_index(const int* sampled_idx, int S, const int64_t* match_
 int unit_paste_masks(const float* probs, const float* boxes, const unsigned char* valid, int S, int M, int H, int W, float threshold,
                      unsigned char* out, void* stream);
 
+/* ---- training metrics (csrc/metrics.hip): the counts behind the ten scalars Detectron2's event storage receives per step, which the
+ * reference reads back with one .item() sync each: rpn/num_{pos,neg}_anchors (modeling/proposal_generator/rpn.py:61-66),
+ * roi_head/num_{fg,bg}_samples (d2 ROIHeads.label_and_sample_proposals behind roi_heads.py:563), fast_rcnn/{cls_accuracy,fg_cls_accuracy,
+ * false_negative} (d2 FastRCNNOutputs._log_accuracy behind fast_rcnn.py:438-445), mask_rcnn/{accuracy,false_positive,false_negative}
+ * (d2 mask_rcnn_loss behind mask_head.py:34). Each call ADDS into int32 counters `m` (five per call) that the caller zeroed with
+ * unit_fill_zero; unit_amd/metrics.py turns a host copy into the scalars. Integer atomics: the totals do not depend on arrival order.
+ * Pointers and ints only (a replayed call list carries them as they are).
+ *   unit_metrics_rpn       labels int8 [n] (unit_subsample_labels' output): m[0] += #(1), m[1] += #(0)
+ *   unit_metrics_fastrcnn  scores fp32 [R][ld], columns col0 .. col0+ncls (ncls = K + 1 <= 96, background = K); roi_cls [R], a value outside
+ *                          [0, K] is an empty slot. pred = argmax by torch.argmax's CPU rule (lowest index among equal maxima; NaN is the
+ *                          largest, the first NaN wins). m[0] instances, m[1] pred == gt, m[2] foreground (gt < K), m[3] foreground with
+ *                          pred == gt, m[4] foreground with pred == K
+ *   unit_metrics_mask      unit_mask_bce_loss's logits / cls / targets; per element of every slot with cls in [0, K), pred = logit[gt class]
+ *                          > 0.0f: m[0] elements, m[1] pred != target, m[2] target set, m[3] pred && !target, m[4] !pred && target */
+int unit_metrics_rpn(const int8_t* labels, int n, int* m, void* stream);
+int unit_metrics_fastrcnn(const float* scores, int ld, int col0, int ncls, const int* roi_cls, int R, int* m, void* stream);
+int unit_metrics_mask(const float* logits, int K, int ldk, const int* cls, const unsigned char* targets, int S, int M, int* m, void* stream);
+
 /* ---- K18 SGD momentum (solver/build.py:110-112) ---- */
 /* lr_dev (may be NULL): device float holding the step's learning rate; `lr` is then the parameter group's multiplier (a captured
  * hipGraph of the step follows the LR schedule: the host rewrites that one float before every replay) */

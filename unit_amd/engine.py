@@ -101,7 +101,7 @@ class GraphedStep:
         self.model, self.optimizer, self.warmup_steps = model, optimizer, warmup_steps
         self.buckets = buckets if (buckets is not None and buckets.active) else None
         self.per_bucket = per_bucket
-        self.graphs = {}          # key -> (graph | (graph A, graph B), static PackedBatch, losses tensor)
+        self.graphs = {}          # key -> (graph | (graph A, graph B), static PackedBatch, losses tensor, (metrics vector | None, its image count))
         self.seen = set()         # keys that have run one eager step (constants uploaded, workspaces sized)
         self.stats = {"eager": 0, "captured": 0, "replayed": 0}          # how the steps so far ran (bench.py --shapes voc: the graph-mode hit rate)
         self.pool = None
@@ -262,7 +262,7 @@ class GraphedStep:
                 self.pool = self.pool or pool
             else:
                 self.pool = self.pool or (g[0] if isinstance(g, tuple) else g).pool()
-            ent = self.graphs[key] = (g, static, losses)
+            ent = self.graphs[key] = (g, static, losses, (model.last_metrics, model.last_metrics_images))
         else:
             self._refill(ent[1], fresh)
         if isinstance(ent[0], tuple) and isinstance(ent[0][0], list):
@@ -278,6 +278,7 @@ class GraphedStep:
             ent[0][1].replay()
         else:
             ent[0].replay()
+        model.last_metrics, model.last_metrics_images = ent[3]          # this key's static vector (another key's step may have run in between)
         opt.iter += 1
         opt._first = False
         return ent[2]
@@ -303,7 +304,7 @@ class ReplayedStep(GraphedStep):
         slot -- a core burnt per rank for nothing (measured: 2 busy threads per process, bench.py `host_cpu_ms_per_step`). With a bound, the host
         sleeps on a blocking HIP event (hipEventBlockingSync: an interrupt, not a poll) until the step `run_ahead` steps back has finished."""
         super().__init__(model, optimizer, warmup_steps=warmup_steps, buckets=buckets, per_bucket=True)
-        self.plans = {}          # key -> (CallList, static PackedBatch, losses tensor)
+        self.plans = {}          # key -> (CallList, static PackedBatch, losses tensor, (metrics vector | None, its image count))
         self.mempool = None
         import collections
         import os
@@ -361,11 +362,12 @@ class ReplayedStep(GraphedStep):
             self.stats["captured"] += 1
             static = fresh.clone()
             plan, losses = self._record(static)          # the recording IS this iteration's step (it ran for real)
-            self.plans[key] = (plan, static, losses)
+            self.plans[key] = (plan, static, losses, (model.last_metrics, model.last_metrics_images))
             return losses
         self.stats["replayed"] += 1
         self._refill(ent[1], fresh)
         ent[0].run()
+        model.last_metrics, model.last_metrics_images = ent[3]
         opt.iter += 1
         opt._first = False
         self._paced()
@@ -375,11 +377,17 @@ class ReplayedStep(GraphedStep):
 class TrainerNoMeta:
     def __init__(self, cfg, model, data_iter=None, weak_data_iter=None, group=None, early_update=False, bf16_buckets=False,
                  use_graph=False, overlap_tail=False, graph_per_bucket=True, high_priority=False, reduce_mode=None, bucket_bytes=None,
-                 use_replay=False):
-        """overlap_tail: the end of a step (last weight gradients, all-reduce waits, SGD, weight re-preparation) stays on the model's
+                 use_replay=False, metrics=False):
+        """metrics: True turns `model.collect_metrics` on -- Detectron2's step scalars are counted on the device inside every step
+        (unit_amd/metrics.py); read them with metrics_dict(). False (the default) leaves the model's own switch as the caller set it.
+        The switch is read when a step is captured / recorded (use_graph, use_replay): a batch key's graph or call list keeps the form
+        it was taken in, so set the switch before the first step and do not flip it afterwards.
+        overlap_tail: the end of a step (last weight gradients, all-reduce waits, SGD, weight re-preparation) stays on the model's
         weight-gradient stream and overlaps the next step's preprocessing / frozen layers (GeneralizedRCNN.overlap_optimizer_tail);
         read parameters between steps only after model.join_optimizer_tail() (state_dict() does it)."""
         self.cfg, self.model = cfg, model
+        if metrics:
+            model.collect_metrics = True
         if high_priority and model.device.type == "cuda":
             # the steps' main chain ahead of the side streams the plan forks (GeneralizedRCNN.high_priority_stream). This makes the
             # high-priority stream the calling thread's CURRENT stream from here on -- whatever the caller enqueues next is ordered
@@ -438,6 +446,17 @@ class TrainerNoMeta:
         if detect_anomaly and not all(math.isfinite(v) for v in vals):
             raise FloatingPointError(f"Loss became infinite or NaN at iteration={self.iter}!\nloss_dict = {d}")
         return d
+
+    def metrics_dict(self):
+        """host copy of the last step's metric counts as Detectron2's scalars (one sync; call sparingly, like loss_dict):
+        rpn/num_{pos,neg}_anchors, roi_head/num_{fg,bg}_samples, fast_rcnn/{cls_accuracy,fg_cls_accuracy,false_negative},
+        mask_rcnn/{accuracy,false_positive,false_negative} -- a key Detectron2 would not have logged for the batch is absent. This
+        process's own batch: no collective. `metrics.put_scalars(storage, ...)` feeds a Detectron2 EventStorage the same way."""
+        from . import metrics as M
+        m = self.model.last_metrics
+        if m is None:
+            raise RuntimeError("metrics_dict(): no metrics were collected -- construct the trainer with metrics=True and run a step")
+        return M.scalars(m.cpu().tolist(), self.model.last_metrics_images)
 
 
 class TrainerFineTune(TrainerNoMeta):

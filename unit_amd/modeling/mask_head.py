@@ -102,15 +102,19 @@ class MaskRCNNConvUpsampleHeadWithSimilarity(nn.Module):
         return y1, lg
 
     # ---- training: mask_rcnn_loss (mean BCE on the gt-class channel over all fg RoIs) + gradient w.r.t. the logits
-    def fwd_train(self, x, cls, targets, loss_out, grad_dtype, sim=None, sim_rows=None, roles=None, dsim=None):
+    def fwd_train(self, x, cls, targets, loss_out, grad_dtype, sim=None, sim_rows=None, roles=None, dsim=None, metrics=None):
         """sim [R,n,b] + sim_rows int32 [S] (RoI row of every fg slot) + roles: the fine-tune configuration's training-time
-        transfer (roi_heads.py:888-906 -> mask_head.py:74-93); dsim [R,n,b] fp32 receives d(loss)/d(sim) of the fg rows (added)."""
+        transfer (roi_heads.py:888-906 -> mask_head.py:74-93); dsim [R,n,b] fp32 receives d(loss)/d(sim) of the fg rows (added).
+        metrics: int32 [5] counters of the mask_rcnn/* scalars (ops.metrics_mask), filled by the base head only -- the fine-tune head's
+        gt-class logit exists only inside unit_mask_bce_loss_ft, so its keys stay absent rather than approximated."""
         y1, lg = self.logits(x)
         s = x.shape[0]
         dlg = torch.empty((s * 196, self.pred.kp), dtype=grad_dtype, device=x.device)
         if sim is None and not self.finetune:
             check(lib().unit_mask_bce_loss(ops._p(lg), self.num_classes, self.pred.kp, ops._p(cls), ops._p(targets), s, self.mask_size, 1.0,
                                            ops._p(loss_out), ops._p(dlg), ops.dt(grad_dtype), ops._s()), "mask_bce_loss")
+            if metrics is not None:
+                ops.metrics_mask(lg, self.num_classes, self.pred.kp, cls, targets, metrics)
         else:
             t = roles or {}
             check(lib().unit_mask_bce_loss_ft(ops._p(lg), self.num_classes, self.pred.kp, self.delta_col0, ops._p(cls), ops._p(targets),

@@ -17,6 +17,7 @@ import os
 import torch
 from torch import nn
 
+from .. import metrics as step_metrics
 from .. import ops
 from ..flat import FlatStore
 from ..structures import (BACKBONE_REGISTRY, META_ARCH_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, ROI_HEADS_REGISTRY, Boxes, ImageList,
@@ -150,6 +151,11 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         self._tail_pending = None
         self.overlap_streams = True
         self.split_weak_head = __import__("os").environ.get("UNIT_SPLIT_WEAK", "1") != "0"     # forward plan: weak_box_head as two 1024-RoI passes
+        # opt-in (TrainerNoMeta(metrics=True)): the counts behind Detectron2's ten step scalars (unit_amd/metrics.py), added into one int32
+        # vector by three small launches inside the step -- no sync; `last_metrics` = the last step's vector (None while the switch is off),
+        # `last_metrics_images` = the number of supervised images it counted over
+        self.collect_metrics = False
+        self.last_metrics, self.last_metrics_images = None, 0
 
     @property
     def device(self):
@@ -378,6 +384,10 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         n_img = n_sup + n_weak
         c.n_sup, c.n_weak = n_sup, n_weak
         c.losses = ops.zeros(len(LOSS_NAMES), torch.float32, self.device)
+        c.metrics = None
+        if self.collect_metrics:
+            c.metrics = ops.zeros(step_metrics.SIZE, torch.int32, self.device)          # (the library's own fill: a recorded call, replayed with the step)
+        self.last_metrics, self.last_metrics_images = c.metrics, n_sup
 
         # a1 preprocess + a2 backbone. The reference runs the backbone once per batch (rcnn.py:439 supervised, :452 weak), each
         # batch zero-padded to ITS OWN largest image (ImageList.from_tensors). When both batches pad to the same size (always
@@ -476,6 +486,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
 
         def rpn_branch():
             c.anchor_labels, c.anchor_match, _ = rpn.label_and_sample_anchors(anchors, batch.gt_boxes, batch.gt_count, perms["rpn"])
+            if c.metrics is not None:
+                ops.metrics_rpn(c.anchor_labels, c.metrics[step_metrics.RPN:step_metrics.RPN + 5])
             _, c.dhead = ops.rpn_loss(head[:n_sup], rpn.num_anchors, rpn.num_anchors, c.anchor_labels, c.anchor_match, batch.gt_boxes,
                                       anchors, rpn.batch_size_per_image * n_sup, dt, loss_out=c.rpn_losses,
                                       weights=(rpn.loss_weight["loss_rpn_cls"], rpn.loss_weight["loss_rpn_loc"]))
@@ -484,7 +496,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             self._reattach_grads()
             main, s2 = torch.cuda.current_stream(), self._rpn_stream
             s2.wait_stream(main)
-            for t in (head, feat, feat_c, anchors, perms["rpn"], c.losses) + tuple(c.rpn_ctx):
+            for t in (head, feat, feat_c, anchors, perms["rpn"], c.losses) + tuple(c.rpn_ctx) + (() if c.metrics is None else (c.metrics,)):
                 t.record_stream(s2)
             with torch.cuda.stream(s2):
                 c.rpn_losses = c.losses[6:8]          # the branch writes its two slots of the loss vector itself; nobody else touches them
@@ -626,6 +638,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 rows = self._const_on_device(("fg_rows", n_sup, s, fgc), lambda: torch.cat([torch.arange(sl.start, sl.stop, dtype=torch.int32) for sl in sel]))
                 c.dsim_mask = torch.zeros(sim.shape, dtype=torch.float32, device=self.device)
                 kw = dict(sim=sim, sim_rows=rows, roles=roles, dsim=c.dsim_mask)
+            if c.metrics is not None:          # (counted by the base mask head only: mask_head.fwd_train)
+                kw["metrics"] = c.metrics[step_metrics.MASK:step_metrics.MASK + 5]
             c.mask_ctx = (mh.fwd_train(x_fg, cls_fg, tgt, c.losses[8:9], dt, **kw), sel)
 
         mask_now = mh is not None and rs > 0 and batch.gt_masks is not None
@@ -671,6 +685,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                                                           wh.oicr_iter, sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"],
                                                           ft=lin_ft, fccol0=bp.col_cls, fbcol0=bp.col_bbox)
                 c.dy_sup = bp.ft_losses(c.scores, bbox, c.roi_cls, c.rois[:rs], c.roi_gt, c.losses[0:2], dt)
+                if c.metrics is not None:          # on the transferred logits, as the reference's FastRCNNOutputs sees them
+                    ops.metrics_fastrcnn(c.scores, 0, rh.num_classes + 1, c.roi_cls, c.metrics[step_metrics.FAST_RCNN:step_metrics.FAST_RCNN + 5])
                 c.ft_ctx = (lin_sup, sims, lingual, keys, t)
                 if mask_now and rh.finetune:        # WSROIHeadWithMaskFineTune hands similarity['seg'][fg] to the mask head
                     run_mask(sims.get("seg"), t)
@@ -681,6 +697,12 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                     sup_side.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(sup_side) if sup_side is not None else contextlib.nullcontext():
                     c.dy_sup, c.scores = bp.sup_losses(lin_sup, lin_weak_sup, c.roi_cls, c.rois[:rs], c.roi_gt, c.losses[0:2], dt)
+                    # behind the losses, on their stream: no edge of its own, but the join below that the main chain already makes for
+                    # the losses (wait_stream(sup_side)) now waits for this launch too (a few microseconds)
+                    if c.metrics is not None:
+                        if sup_side is not None:
+                            c.metrics.record_stream(sup_side)
+                        ops.metrics_fastrcnn(c.scores, 0, rh.num_classes + 1, c.roi_cls, c.metrics[step_metrics.FAST_RCNN:step_metrics.FAST_RCNN + 5])
                 c.sup_losses_on_head_stream = sup_side is not None
         if rw > 0:
             c.dy_weak = bp.weak_detector_head.fused_losses(lin_weak_w, c.rois[rs:], c.weak_valid, s // rh.weak_divisor, n_weak,

@@ -1697,3 +1697,28 @@ def sum_losses(losses, out=None):
 def sgd_momentum(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, first_step=False, lr_dev=None):
     check(lib().unit_sgd_momentum(_p(p), _p(g), _p(buf), p.numel(), float(lr), float(momentum), float(weight_decay), float(grad_scale),
                                   int(first_step), _p(lr_dev), _s()), "sgd_momentum")
+
+
+# ------------------------------------------------------------------------------------------------ training metrics (csrc/metrics.hip)
+def metrics_rpn(labels, m):
+    """m[0] += #(label == 1), m[1] += #(label == 0) over the sampled anchor labels (int8, any shape); m: int32 counters, zeroed by the caller"""
+    assert labels.dtype == torch.int8 and labels.is_contiguous() and m.dtype == torch.int32 and m.numel() >= 2
+    check(lib().unit_metrics_rpn(_p(labels), labels.numel(), _p(m), _s()), "metrics_rpn")
+
+
+def metrics_fastrcnn(scores, col0, ncls, roi_cls, m):
+    """the counts behind fast_rcnn/* and roi_head/* of one classifier batch: scores fp32 [R, ld] (columns col0 .. col0 + ncls, background last),
+    roi_cls int32 [R] (outside [0, ncls - 1]: empty slot) -> m[0..5) += instances, correct, foreground, foreground correct, foreground called
+    background"""
+    r, ld = scores.shape
+    assert scores.dtype == torch.float32 and scores.stride(1) == 1 and roi_cls.dtype == torch.int32 and roi_cls.numel() == r
+    assert m.dtype == torch.int32 and m.numel() >= 5
+    check(lib().unit_metrics_fastrcnn(_p(scores), scores.stride(0) if r > 1 else ld, col0, ncls, _p(roi_cls), r, _p(m), _s()), "metrics_fastrcnn")
+
+
+def metrics_mask(logits, k, ldk, cls, targets, m):
+    """the counts behind mask_rcnn/*: logits / cls / targets as unit_mask_bce_loss takes them (targets uint8 [S, M, M]) -> m[0..5) += elements,
+    wrong, positives, false positives, false negatives"""
+    s, msz = targets.shape[0], targets.shape[-1]
+    assert logits.dtype == torch.float32 and cls.dtype == torch.int32 and targets.dtype == torch.uint8 and m.dtype == torch.int32 and m.numel() >= 5
+    check(lib().unit_metrics_mask(_p(logits), k, ldk, _p(cls), _p(targets), s, msz, _p(m), _s()), "metrics_mask")
