@@ -165,8 +165,9 @@ typedef struct UnitConvSecond {
 int unit_conv2d_fwd_pair(int kernel, const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref, int mask_c,
                          int in_dtype, int out_dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy,
                          int oy_mul, int OHf, int OWf, int relu, int tile, const UnitConvSecond* second, void* stream);
+/* = unit_conv2d_wgrad_splits(...) * K*R*S*C * sizeof(float): the query, the split count and the launch ask ONE decision function */
 size_t unit_conv2d_wgrad_workspace_bytes(int in_dtype, int N, int OH, int OW, int K, int R, int S, int C);
-/* variant: 0 = production policy. Big-M bf16 layers (C % 256 == 0, K % 256 == 0, M >= 16384) use a 256x256 tile: policy = the
+/* variant: 0 = production policy. Big-M bf16 layers (C % 256 == 0, K % 256 == 0, M >= 16384, or M >= 8192 with >= 96 tiles) use a 256x256 tile: policy = the
  * phase-interleaved schedule (csrc/conv_wgrad256p8.hip) for pointwise layers and maps of <= 1024 pixels -- on 3x3 s1 p1 convs over maps
  * of <= 512 pixels contracting only over the pixels whose filter tap lies inside the map (18 % fewer steps on 7x7; equal to the full
  * contraction within fp32 rounding, deterministic) -- and a ring of four 32-pixel stages (csrc/conv_wgrad256r.hip) otherwise;

@@ -461,6 +461,80 @@ def test_wgrad_group_rejects_ineligible_layers(dev):
         o.conv2d_wgrad_group([(x, dy, 128, 1, 1, 1, 0)])
 
 
+def test_wgrad_group_supported_on_parts_needs_every_part(dev):
+    o = ops()
+    mk = lambda n, h, w, c, dtype=torch.bfloat16: torch.zeros(n, h, w, c, dtype=dtype, device=dev)
+    xs, dys = [mk(1, 10, 12, 128), mk(1, 8, 14, 128)], [mk(1, 5, 6, 128), mk(1, 4, 7, 128)]
+    assert o.wgrad_group_supported(o.Parts(xs), o.Parts(dys), 128, 3, 3, 2, 1)
+    # one eligible part + one that is not (fp32 operands; no pixels at all)
+    assert not o.wgrad_group_supported(o.Parts([xs[0], mk(1, 8, 14, 128, torch.float32)]), o.Parts([dys[0], mk(1, 4, 7, 128, torch.float32)]), 128, 3, 3, 2, 1)
+    assert not o.wgrad_group_supported(o.Parts([mk(0, 8, 14, 128), xs[0]]), o.Parts([mk(0, 4, 7, 128), dys[0]]), 128, 3, 3, 2, 1)
+
+
+# rows of tests/test_wgrad_select_cpu.py's table that run on the GPU: (N, H, W, C, K, R = S, stride, pad, dtype)
+WGRAD_ROWS = {"a": (2, 9, 11, 32, 32, 3, 1, 1, torch.float32), "b": (2, 9, 11, 64, 64, 3, 1, 1, torch.bfloat16),
+              "c": (2, 10, 12, 128, 128, 3, 2, 1, torch.bfloat16), "e": (2, 96, 96, 256, 256, 1, 1, 0, torch.bfloat16),
+              "f": (2, 96, 96, 256, 256, 3, 1, 1, torch.bfloat16)}
+
+
+def _wgrad_operands(o, dev, gen, n, h, w, c, k, r, stride, pad, dtype):
+    oh, ow = o.conv_out_size(h, w, r, r, stride, pad)
+    return torch.randn(n, h, w, c, generator=gen).to(dtype).to(dev), (torch.randn(n, oh, ow, k, generator=gen) * 0.25).to(dtype).to(dev)
+
+
+def _slab_bits(slab, floats):
+    return slab.view(torch.int32)[:floats].clone()
+
+
+@pytest.mark.parametrize("row", sorted(WGRAD_ROWS))
+def test_wgrad_partial_plus_reduce_is_conv2d_wgrad_bit_for_bit(dev, row):
+    """the slabs conv2d_wgrad_partial leaves, added in slab order in fp32 and scaled per filter (what wgrad_reduce_kernel does:
+    sp = 0.., then scale[n]; no contraction on either side), are conv2d_wgrad's result exactly -- one kernel family per row:
+    fp32 and bf16 register-staged, 128x128 ring, 256x256 phase-interleaved and ring"""
+    o = ops()
+    n, h, w, c, k, r, stride, pad, dtype = WGRAD_ROWS[row]
+    gen = g(61)
+    x, dy = _wgrad_operands(o, dev, gen, n, h, w, c, k, r, stride, pad, dtype)
+    scale = (torch.rand(k, generator=gen) + 0.5).to(dev)
+    slab, sp = o.conv2d_wgrad_partial(x, dy, k, r, r, stride, pad)
+    oh, ow = o.conv_out_size(h, w, r, r, stride, pad)
+    assert sp == o.lib().unit_conv2d_wgrad_splits(o.dt(dtype), n, oh, ow, k, r, r, c)
+    parts = slab.view(torch.float32)[:sp * k * r * r * c].view(sp, k, r, r, c)
+    acc = parts[0].clone()
+    for i in range(1, sp):
+        acc += parts[i]
+    acc *= scale.view(-1, 1, 1, 1)
+    ref = o.conv2d_wgrad(x, dy, k, r, r, stride, pad, scale=scale)
+    assert torch.equal(acc.view(torch.int32), ref.view(torch.int32))
+
+
+@pytest.mark.parametrize("row,maps", [("c", ((1, 10, 12), (1, 8, 14))), ("e", ((2, 96, 96), (2, 90, 100)))])
+def test_wgrad_partial_of_parts_is_its_parts_end_to_end(dev, row, maps):
+    """ops.Parts operands (the image groups of a ragged batch through a non-pointwise layer): n_splits is the sum of the parts' own counts
+    and the slab holds the parts' slabs one after the other, bit for bit; a slab too small comes back regrown, a large enough one
+    is reused"""
+    o = ops()
+    _, _, _, c, k, r, stride, pad, dtype = WGRAD_ROWS[row]
+    gen = g(67)
+    ops_ = [_wgrad_operands(o, dev, gen, n, h, w, c, k, r, stride, pad, dtype) for n, h, w in maps]
+    one = k * r * r * c
+    per = [o.conv2d_wgrad_partial(x, dy, k, r, r, stride, pad) for x, dy in ops_]
+    want = torch.cat([_slab_bits(slab, sp * one) for slab, sp in per])
+    xs, dys = o.Parts(x for x, _ in ops_), o.Parts(dy for _, dy in ops_)
+    slab, sp = o.conv2d_wgrad_partial(xs, dys, k, r, r, stride, pad)
+    assert sp == sum(s for _, s in per) and slab.numel() >= sp * one * 4
+    assert torch.equal(_slab_bits(slab, sp * one), want)
+    small = torch.empty(one * 4, dtype=torch.uint8, device=dev)
+    assert small.numel() < sp * one * 4
+    slab2, sp2 = o.conv2d_wgrad_partial(xs, dys, k, r, r, stride, pad, slab=small)
+    assert slab2 is not small and slab2.numel() >= sp * one * 4 and sp2 == sp
+    assert torch.equal(_slab_bits(slab2, sp * one), want)
+    slab2.zero_()
+    slab3, sp3 = o.conv2d_wgrad_partial(xs, dys, k, r, r, stride, pad, slab=slab2)
+    assert slab3 is slab2 and sp3 == sp
+    assert torch.equal(_slab_bits(slab3, sp * one), want)
+
+
 @pytest.mark.parametrize("case,tile", [((1024, 7, 7, 512, 512, 3, 1, 1), 16), ((1024, 7, 7, 512, 2048, 1, 1, 0), 16), ((1024, 7, 7, 2048, 512, 1, 1, 0), 16),
                                        ((1024, 14, 14, 1024, 512, 1, 2, 0), 16), ((4, 38, 63, 1024, 1024, 3, 1, 1), 16),
                                        ((1024, 7, 7, 512, 512, 3, 1, 1), 21), ((1024, 7, 7, 512, 2048, 1, 1, 0), 21), ((1024, 7, 7, 2048, 512, 1, 1, 0), 21),

@@ -253,6 +253,34 @@ def test_wgrad_x3(dev, case, wgrad_passes):
     assert torch.allclose(dw2, 2 * dw, rtol=1e-5, atol=1e-6 * s)
 
 
+def test_wgrad_x3_partial_of_parts_is_its_parts_end_to_end(dev, wgrad_passes):
+    """ops.Parts of split tensors (3x3 s2 p1, 128 -> 128 channels, two image groups of different map size): n_splits is the sum of the parts'
+    own counts (passes x splits each), the slab holds the parts' slabs one after the other bit for bit; a slab too small comes back regrown,
+    a large enough one is reused"""
+    o = ops()
+    c, k, r, stride, pad = 128, 128, 3, 2, 1
+    gen = g(71)
+    pairs = []
+    for n, h, w in ((1, 10, 12), (1, 8, 14)):
+        oh, ow = o.conv_out_size(h, w, r, r, stride, pad)
+        pairs.append((o.x3_split(torch.randn(n, h, w, c, generator=gen).to(dev)), o.x3_split((torch.randn(n, oh, ow, k, generator=gen) / 8).to(dev))))
+    one = k * r * r * c
+    bits = lambda slab, sp: slab.view(torch.int32)[:sp * one].clone()
+    per = [o.conv2d_wgrad_partial(xs, dys, k, r, r, stride, pad) for xs, dys in pairs]
+    assert all(sp % wgrad_passes == 0 for _, sp in per)
+    want = torch.cat([bits(slab, sp) for slab, sp in per])
+    xp, dp = o.Parts(xs for xs, _ in pairs), o.Parts(dys for _, dys in pairs)
+    slab, sp = o.conv2d_wgrad_partial(xp, dp, k, r, r, stride, pad)
+    assert sp == sum(s for _, s in per) and torch.equal(bits(slab, sp), want)
+    small = torch.empty(one * 4, dtype=torch.uint8, device=dev)
+    assert small.numel() < sp * one * 4
+    slab2, sp2 = o.conv2d_wgrad_partial(xp, dp, k, r, r, stride, pad, slab=small)
+    assert slab2 is not small and slab2.numel() >= sp * one * 4 and sp2 == sp and torch.equal(bits(slab2, sp), want)
+    slab2.zero_()
+    slab3, sp3 = o.conv2d_wgrad_partial(xp, dp, k, r, r, stride, pad, slab=slab2)
+    assert slab3 is slab2 and sp3 == sp and torch.equal(bits(slab3, sp), want)
+
+
 def test_avgpool_x3(dev):
     o = ops()
     r, c = 37, 256

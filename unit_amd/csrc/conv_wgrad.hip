@@ -8,20 +8,7 @@
 // The m-range is split across workgroups (split-M); partial fp32 slabs go to the workspace and unit_wgrad_reduce sums
 // them in a fixed order (bit-reproducible), applies the FrozenBN scale[n] fold and writes / accumulates dW [K][R][S][C].
 #include "common.h"
-#include "conv_wgrad256.h"
-
-struct WgradArgs {
-  const void* x; const void* dy; float* partial;
-  int N, H, W, C;
-  int K, R, S, stride, pad;
-  int OH, OW;
-  int ldy;     // dy row stride (elements)
-  int Kgemm, M;
-  int tiles_k, tiles_n, splits, m_per_split;
-  unsigned x_bytes, dy_bytes;
-  unsigned magic_ohw, magic_ow; int OHW; int use_magic;
-  int x_pitch;     // elements per pixel row of x (Wgrad256Args::x_pitch)
-};
+#include "conv_wgrad_host.h"
 
 template <typename TI> struct WgCfg;
 template <> struct WgCfg<bf16_t> { static constexpr int ROWB = 288, MS = 64, EPC = 8; };   // 128 elems * 2 B + 32 pad
@@ -62,7 +49,7 @@ template <> struct WgFrag<float> {
 };
 
 template <typename TI>
-__global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(WgradArgs p) {
+__global__ void __launch_bounds__(256, 2) conv_wgrad_kernel(Wgrad256Args p) {
   typedef WgCfg<TI> Cfg;
   constexpr int ROWB = Cfg::ROWB, MS = Cfg::MS, EPC = Cfg::EPC;
   constexpr int BK = 128, BN = 128;
@@ -201,48 +188,11 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int split
   *reinterpret_cast<f32x4*>(dw + i) = s;
 }
 
-// conv_wgrad256.hip: 256x256 LDS-DMA kernel for the big-M bf16 layers (same slab layout)
-extern "C" int unit_wgrad_use_big(int in_dtype, long M, int K, int C, int RS);
-extern "C" int unit_wgrad_big_splits(long M, int tiles, int R, int S, int OHW);
-// (x_pitch: elements per pixel row of x, x_span / dy_span: bytes from x / dy to the end of their tensors -- Wgrad256Args::x_pitch)
-int unit_conv2d_wgrad_big_launch_p(const void* x, const void* dy, float* partial, int N, int H, int W, int C, int K, int R, int S,
-                                   int stride, int pad, int OH, int OW, int ldy, int variant, size_t workspace_bytes, int x_pitch, size_t x_span,
-                                   size_t dy_span, void* stream);
-
-// 128x128 tile: the LDS-DMA ring kernel (conv_wgrad128r.hip) where it applies (bf16, C % 128 == 0, K % 128 == 0), variant 4 = the
-// register-staged kernel below everywhere. Isolated the two are equal on the backbone shapes (tools/wgrad128_bench.py: 18.2 vs 18.5 us,
-// 31.9 vs 30.4 us; RPN 3x3 306 vs 284 us -- at M = 9 576 these launches are bound by their fp32 slab store and input streaming, not by
-// the loop's load latency); inside the step the ring form is 0.05-0.1 ms ahead on the same box (18.36 vs 18.44-18.48 ms).
-static int choose_splits(int M, int tiles, int ms) {
-  // 2 workgroups of this kernel are co-resident per CU (72 KB LDS each): 512 slots per "round" on 256 CUs. Pick the
-  // split count whose grid fills whole rounds best (tile quantisation), preferring fewer splits (less slab traffic).
-  // Cost model (us), fitted to tools/microbench.py on the res3/res4/RPN shapes: a workgroup needs ~4 us of fixed time
-  // (launch ramp, first loads, slab store) plus ~1.0 us per staged 64-row step (operand-feed bound at this tile); the
-  // grid runs in rounds of 512 workgroups; every split writes one fp32 slab of the whole dW (64 KB per tile) that the
-  // reduction reads back: ~2 x 64 KB per tile and split at ~4 TB/s.
-  int maxs = (M + 4 * ms - 1) / (4 * ms);   // at least 4 staged steps per split
-  if (maxs < 1) maxs = 1;
-  if (maxs > 64) maxs = 64;
-  int best = 1; double best_cost = 1e30;
-  double steps_total = (double)((M + ms - 1) / ms);
-  for (int s = 1; s <= maxs; ++s) {
-    long blocks = (long)tiles * s;
-    long rounds = (blocks + 511) / 512;
-    double per_block = 4.0 + 1.0 * (steps_total / s) * (ms / 64.0);
-    double slab = (double)blocks * 2.0 * 65536.0 / 4.0e6;      // bytes / (4 TB/s) in us
-    double cost = rounds * per_block + slab;
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
+// conv_wgrad256.hip: the 256x256 tile's kernels for the big-M bf16 layers (same slab layout) on a filled argument block
+int unit_wgrad_big_launch_args(Wgrad256Args& a, int variant, size_t workspace_bytes, hipStream_t st);
 
 extern "C" size_t unit_conv2d_wgrad_workspace_bytes(int in_dtype, int N, int OH, int OW, int K, int R, int S, int C) {
-  long M = (long)N * OH * OW;
-  int Kgemm = R * S * C;
-  if (unit_wgrad_use_big(in_dtype, M, K, C, R * S)) return (size_t)unit_wgrad_big_splits(M, (Kgemm / 256) * (K / 256), R, S, OH * OW) * K * Kgemm * sizeof(float);
-  int tiles = cdiv(Kgemm, 128) * cdiv(K, 128);
-  int splits = choose_splits((int)M, tiles, in_dtype == UNIT_BF16 ? 64 : 32);
-  return (size_t)splits * K * Kgemm * sizeof(float);
+  return (size_t)wgrad_select(in_dtype, N, OH, OW, K, R, S, C).splits * K * R * S * C * sizeof(float);
 }
 
 // one pass of split-M slabs into `workspace` (no reduction); returns the number of slabs written or a negative status.
@@ -254,40 +204,20 @@ static int wgrad_pass(const void* x, const void* dy, int in_dtype, int N, int H,
   int epc = in_dtype == UNIT_BF16 ? 8 : 4;
   UNIT_CHECK_ARG(C % epc == 0 && K % epc == 0 && ldy % epc == 0, "wgrad: C, K, ldy must be multiples of 8 (bf16) / 4 (fp32)");
   UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0), "wgrad: 16B alignment");
-  WgradArgs a;
-  a.x = x; a.dy = dy; a.partial = (float*)workspace; a.x_pitch = x_pitch;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.OH = OH; a.OW = OW;
-  a.ldy = ldy; a.Kgemm = R * S * C; a.M = N * OH * OW;
-  UNIT_CHECK_ARG(a.Kgemm % 4 == 0, "wgrad: R*S*C % 4 != 0");
-  size_t xb = x_span, db = dy_span;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && db < 0xFFFFFFF0ull, "wgrad: operand larger than 4 GiB");
-  a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)db;
-  a.OHW = OH * OW;
-  a.use_magic = ((unsigned long long)(a.M + 64) * (unsigned long long)a.OHW < 0xFFFFFFFFull) ? 1 : 0;
-  // ceil(2^32 / d); for d == 1 the quotient is m itself: magic 0xFFFFFFFF gives m-1 for m>0 and the correction fixes it
-  a.magic_ohw = a.OHW > 1 ? (unsigned)((0x100000000ull + a.OHW - 1) / (unsigned long long)a.OHW) : 0xFFFFFFFFu;
-  a.magic_ow = OW > 1 ? (unsigned)((0x100000000ull + OW - 1) / (unsigned long long)OW) : 0xFFFFFFFFu;
+  UNIT_CHECK_ARG(R * S * C % 4 == 0, "wgrad: R*S*C % 4 != 0");
+  const WgradChoice ch = wgrad_select(in_dtype, N, OH, OW, K, R, S, C);
+  Wgrad256Args a;
+  int rc = wgrad_fill(a, "wgrad: operand larger than 4 GiB", x, dy, (float*)workspace, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy, x_pitch,
+                      x_span, dy_span, ch.tile, ch.ms, ch.splits);
+  if (rc != UNIT_OK) return rc;
   hipStream_t st = (hipStream_t)stream;
-  if (unit_wgrad_use_big(in_dtype, a.M, K, C, R * S))
-    return unit_conv2d_wgrad_big_launch_p(x, dy, (float*)workspace, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy, variant <= 3 ? variant : 0,
-                                          workspace_bytes, x_pitch, x_span, dy_span, stream);
-  a.tiles_k = cdiv(a.Kgemm, 128); a.tiles_n = cdiv(K, 128);
-  int ms = in_dtype == UNIT_BF16 ? 64 : 32;
-  a.splits = choose_splits(a.M, a.tiles_k * a.tiles_n, ms);
-  int mps = cdiv(a.M > 0 ? a.M : 1, a.splits);
-  a.m_per_split = cdiv(mps, ms) * ms;
+  if (ch.family == WGRAD_BIG) return unit_wgrad_big_launch_args(a, variant <= 3 ? variant : 0, workspace_bytes, st);
   size_t need = (size_t)a.splits * K * a.Kgemm * sizeof(float);
   if (workspace_bytes < need) { unit_set_error("wgrad: workspace too small"); return UNIT_ERR_WORKSPACE; }
   int grid = a.tiles_k * a.tiles_n * a.splits;
   // bf16 layers whose tiles are full (every trainable backbone / RPN conv): LDS-DMA ring kernel (conv_wgrad128r.hip), same slabs
-  if (in_dtype == UNIT_BF16 && C % 128 == 0 && K % 128 == 0 && variant != 4) {
-    Wgrad256Args b;
-    b.x = a.x; b.dy = a.dy; b.partial = a.partial; b.N = a.N; b.H = a.H; b.W = a.W; b.C = a.C; b.K = a.K; b.R = a.R; b.S = a.S;
-    b.stride = a.stride; b.pad = a.pad; b.OH = a.OH; b.OW = a.OW; b.ldy = a.ldy; b.Kgemm = a.Kgemm; b.M = a.M;
-    b.tiles_k = a.tiles_k; b.tiles_n = a.tiles_n; b.splits = a.splits; b.m_per_split = a.m_per_split;
-    b.x_bytes = a.x_bytes; b.dy_bytes = a.dy_bytes; b.magic_ohw = a.magic_ohw; b.magic_ow = a.magic_ow; b.OHW = a.OHW; b.use_magic = a.use_magic; b.valid_only = 0;
-    b.x_pitch = a.x_pitch;
-    int rc = unit_wgrad128_ring_launch(b, st);
+  if (ch.family == WGRAD_RING128 && variant != 4) {
+    rc = unit_wgrad128_ring_launch(a, st);
     if (rc != UNIT_OK) return rc;
   } else if (in_dtype == UNIT_BF16) {
     size_t lds = (size_t)2 * 2 * WgCfg<bf16_t>::MS * WgCfg<bf16_t>::ROWB;
@@ -354,10 +284,7 @@ extern "C" int unit_conv2d_wgrad_x3(const void* x, const void* dy, float* dw, co
 
 // number of split-M slabs unit_conv2d_wgrad writes for this shape (slab s at workspace + s*K*R*S*C floats)
 extern "C" int unit_conv2d_wgrad_splits(int in_dtype, int N, int OH, int OW, int K, int R, int S, int C) {
-  long M = (long)N * OH * OW;
-  if (unit_wgrad_use_big(in_dtype, M, K, C, R * S)) return unit_wgrad_big_splits(M, (R * S * C / 256) * (K / 256), R, S, OH * OW);
-  int tiles = cdiv(R * S * C, 128) * cdiv(K, 128);
-  return choose_splits((int)M, tiles, in_dtype == UNIT_BF16 ? 64 : 32);
+  return wgrad_select(in_dtype, N, OH, OW, K, R, S, C).splits;
 }
 
 // ---- grouped launches (conv_wgrad128r.hip: conv_wgrad128_group_kernel; conv_wgrad256p8.hip: conv_wgrad256_group_kernel) -------------
@@ -470,22 +397,13 @@ static int wgrad_group_fill(const UnitWgradProblem& q, Wgrad256Args& b) {
   UNIT_CHECK_ARG(((uintptr_t)q.x % 16 == 0) && ((uintptr_t)q.dy % 16 == 0) && ((uintptr_t)q.partial % 16 == 0) && q.partial != nullptr,
                  "wgrad_group: 16B alignment");
   UNIT_CHECK_ARG(q.splits >= 1 && q.splits <= WG_GROUP_MAX_SPLITS, "wgrad_group: splits 1..127 (unit_conv2d_wgrad_group_plan)");
-  b.x = q.x; b.dy = q.dy; b.partial = (float*)q.partial;
-  b.N = q.N; b.H = q.H; b.W = q.W; b.C = q.C; b.K = q.K; b.R = q.R; b.S = q.S; b.stride = q.stride; b.pad = q.pad; b.OH = q.OH; b.OW = q.OW;
-  b.ldy = q.ldy; b.Kgemm = q.R * q.S * q.C; b.M = q.N * q.OH * q.OW;
-  UNIT_CHECK_ARG(b.M > 0, "wgrad_group: empty problem");
-  b.x_pitch = q.x_pitch > 0 ? q.x_pitch : q.C;
-  UNIT_CHECK_ARG(b.x_pitch >= q.C && b.x_pitch % 8 == 0 && q.x_back >= 0 && q.dy_back >= 0, "wgrad_group: x_pitch / x_back / dy_back");
-  size_t xb = ((size_t)q.N * q.H * q.W * b.x_pitch - q.x_back) * 2, db = ((size_t)b.M * q.ldy - q.dy_back) * 2;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && db < 0xFFFFFFF0ull, "wgrad_group: operand larger than 4 GiB");
-  b.x_bytes = (unsigned)xb; b.dy_bytes = (unsigned)db;
-  b.OHW = q.OH * q.OW;
-  b.use_magic = ((unsigned long long)(b.M + 64) * (unsigned long long)b.OHW < 0xFFFFFFFFull) ? 1 : 0;
-  b.magic_ohw = b.OHW > 1 ? (unsigned)((0x100000000ull + b.OHW - 1) / (unsigned long long)b.OHW) : 0xFFFFFFFFu;
-  b.magic_ow = q.OW > 1 ? (unsigned)((0x100000000ull + q.OW - 1) / (unsigned long long)q.OW) : 0xFFFFFFFFu;
-  b.tiles_k = b.Kgemm / T; b.tiles_n = q.K / T;
-  b.splits = q.splits;
-  b.m_per_split = cdiv(cdiv(b.M, q.splits), 64) * 64;
+  UNIT_CHECK_ARG(q.N * q.OH * q.OW > 0, "wgrad_group: empty problem");
+  const int x_pitch = q.x_pitch > 0 ? q.x_pitch : q.C;
+  UNIT_CHECK_ARG(x_pitch >= q.C && x_pitch % 8 == 0 && q.x_back >= 0 && q.dy_back >= 0, "wgrad_group: x_pitch / x_back / dy_back");
+  int rc = wgrad_fill(b, "wgrad_group: operand larger than 4 GiB", q.x, q.dy, (float*)q.partial, q.N, q.H, q.W, q.C, q.K, q.R, q.S, q.stride, q.pad,
+                      q.OH, q.OW, q.ldy, x_pitch, ((size_t)q.N * q.H * q.W * x_pitch - q.x_back) * 2,
+                      ((size_t)q.N * q.OH * q.OW * q.ldy - q.dy_back) * 2, T, 64, q.splits);
+  if (rc != UNIT_OK) return rc;
   b.valid_only = (q.kind == 2 && group_valid_only(q)) ? 1 : 0;
   UNIT_CHECK_ARG(b.tiles_k * b.tiles_n <= 4096, "wgrad_group: more than 4096 tiles in one layer");
   return UNIT_OK;

@@ -1,5 +1,6 @@
-// conv_wgrad256.h -- argument block shared by the 256x256-tile weight-gradient kernels (conv_wgrad256.hip: two-stage loop;
-// conv_wgrad256p8.hip: four phases per 64-pixel step, half-tile staging under a counted vmcnt).
+// conv_wgrad256.h -- argument block of EVERY weight-gradient kernel (it began with the 256x256 tiles -- conv_wgrad256.hip: two-stage loop;
+// conv_wgrad256p8.hip: four phases per 64-pixel step, half-tile staging under a counted vmcnt; conv_wgrad256r.hip -- and now also serves the
+// 128x128 tiles of conv_wgrad128r.hip and conv_wgrad.hip). Filled by wgrad_fill (conv_wgrad_host.h) and nowhere else.
 #pragma once
 #include "common.h"
 

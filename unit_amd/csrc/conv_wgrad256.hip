@@ -10,7 +10,7 @@
 // banks), so 32-B column blocks are XOR-swizzled with (row & 7) on the DMA source side; a half-wave of the transposing
 // read then touches 8 rows x 32 B on 8 different bank groups.
 // Requires bf16, C % 256 == 0 (a k-tile stays inside one filter tap) and K % 256 == 0.
-#include "conv_wgrad256.h"
+#include "conv_wgrad_host.h"
 
 __device__ __forceinline__ bf16x8 tr_frag(const char* tile, int sub, int col0, int lane) {
   // lane l: g = l>>4, i = l&15 = 4q+p ; reads rows (32*sub + 16h + 4g + q), cols col0 + 4p..4p+3 ; element j=4h+q' of
@@ -187,40 +187,23 @@ extern "C" int unit_wgrad_big_splits_base(long M, int tiles) {
   return best;
 }
 
-int unit_conv2d_wgrad_big_launch_p(const void* x, const void* dy, float* partial, int N, int H, int W, int C, int K, int R, int S,
-                                   int stride, int pad, int OH, int OW, int ldy, int variant, size_t workspace_bytes, int x_pitch, size_t x_span,
-                                   size_t dy_span, void* stream) {
-  Wgrad256Args a;
-  a.x = x; a.dy = dy; a.partial = partial; a.x_pitch = x_pitch;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.OH = OH; a.OW = OW;
-  a.ldy = ldy; a.Kgemm = R * S * C; a.M = N * OH * OW;
-  UNIT_CHECK_ARG(ldy % 8 == 0, "wgrad_big: ldy must be a multiple of 8");
-  size_t xb = x_span, db = dy_span;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && db < 0xFFFFFFF0ull, "wgrad_big: operand larger than 4 GiB");
-  a.x_bytes = (unsigned)xb; a.dy_bytes = (unsigned)db;
-  a.OHW = OH * OW;
-  a.use_magic = ((unsigned long long)(a.M + 64) * (unsigned long long)a.OHW < 0xFFFFFFFFull) ? 1 : 0;
-  a.magic_ohw = a.OHW > 1 ? (unsigned)((0x100000000ull + a.OHW - 1) / (unsigned long long)a.OHW) : 0xFFFFFFFFu;
-  a.magic_ow = OW > 1 ? (unsigned)((0x100000000ull + OW - 1) / (unsigned long long)OW) : 0xFFFFFFFFu;
-  a.tiles_k = a.Kgemm / 256; a.tiles_n = K / 256;
-  a.splits = unit_wgrad_big_splits(a.M, a.tiles_k * a.tiles_n, R, S, OH * OW);
-  int mps = cdiv(a.M, a.splits);
-  a.m_per_split = cdiv(mps, 64) * 64;
-  size_t need = (size_t)a.splits * K * a.Kgemm * sizeof(float);
+// launches the 256x256 tile on a filled argument block; returns the number of slabs written or a negative status
+int unit_wgrad_big_launch_args(Wgrad256Args& a, int variant, size_t workspace_bytes, hipStream_t st) {
+  UNIT_CHECK_ARG(a.ldy % 8 == 0, "wgrad_big: ldy must be a multiple of 8");
+  size_t need = (size_t)a.splits * a.K * a.Kgemm * sizeof(float);
   if (workspace_bytes < need) { unit_set_error("wgrad_big: workspace too small"); return UNIT_ERR_WORKSPACE; }
   // variant (include/unit_hip.h): 0 = policy, 1 = two-stage, 2 = ring, 3 = phase-interleaved over all pixels
-  a.valid_only = 0;
   if (variant == 0) {
-    variant = ((R == 1 && S == 1 && stride == 1 && pad == 0) || OH * OW <= 1024) ? 3 : 2;
+    variant = ((a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) || a.OHW <= 1024) ? 3 : 2;
     // 3x3 s1 p1 "same" conv on a small map: contract only over the pixels whose tap lies inside the map (Wgrad256Args::valid_only)
-    if (variant == 3 && R == 3 && S == 3 && stride == 1 && pad == 1 && OH == H && OW == W && OH * OW <= 512) a.valid_only = 1;
+    if (variant == 3 && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W && a.OHW <= 512) a.valid_only = 1;
   }
   if (variant == 3) {
-    int rc = unit_wgrad256_p8_launch(a, (hipStream_t)stream);
+    int rc = unit_wgrad256_p8_launch(a, st);
     return rc == UNIT_OK ? a.splits : rc;
   }
   if (variant == 2) {
-    int rc = unit_wgrad256_ring_launch(a, (hipStream_t)stream);
+    int rc = unit_wgrad256_ring_launch(a, st);
     return rc == UNIT_OK ? a.splits : rc;
   }
   size_t lds = 2 * 2 * 64 * 512;
@@ -229,13 +212,19 @@ int unit_conv2d_wgrad_big_launch_p(const void* x, const void* dy, float* partial
     (void)hipFuncSetAttribute((const void*)conv_wgrad256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
-  conv_wgrad256_kernel<<<a.tiles_k * a.tiles_n * a.splits, 512, lds, (hipStream_t)stream>>>(a);
+  conv_wgrad256_kernel<<<a.tiles_k * a.tiles_n * a.splits, 512, lds, st>>>(a);
   UNIT_LAUNCH_CHECK();
   return a.splits;
 }
 
+// the 256x256 tile whatever the policy says (tests, tools): plain bf16 tensors
 extern "C" int unit_conv2d_wgrad_big_launch(const void* x, const void* dy, float* partial, int N, int H, int W, int C, int K, int R, int S,
                                             int stride, int pad, int OH, int OW, int ldy, int variant, size_t workspace_bytes, void* stream) {
-  return unit_conv2d_wgrad_big_launch_p(x, dy, partial, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy, variant, workspace_bytes, C,
-                                        (size_t)N * H * W * C * 2, (size_t)N * OH * OW * ldy * 2, stream);
+  UNIT_CHECK_ARG(C % 256 == 0 && K % 256 == 0, "wgrad_big: C, K must be multiples of 256");
+  const WgradChoice ch = wgrad_select(UNIT_BF16, N, OH, OW, K, R, S, C, true);
+  Wgrad256Args a;
+  int rc = wgrad_fill(a, "wgrad_big: operand larger than 4 GiB", x, dy, partial, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy, C,
+                      (size_t)N * H * W * C * 2, (size_t)N * OH * OW * ldy * 2, ch.tile, ch.ms, ch.splits);
+  if (rc != UNIT_OK) return rc;
+  return unit_wgrad_big_launch_args(a, variant, workspace_bytes, (hipStream_t)stream);
 }

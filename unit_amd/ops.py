@@ -307,7 +307,10 @@ PROFILER = None
 
 class _timed:
     """`with _timed("name", flops, bytes):` -- when bench.py has set PROFILER, brackets the launches inside with a HIP-event pair on
-    the launch stream and files (e0, e1, flops, algorithmic bytes) under `name`; free otherwise"""
+    the launch stream and files (e0, e1, flops, algorithmic bytes, ref_bytes | None) under `name`; free otherwise. Figures that cost
+    something to work out are set inside the block (`as t: ... if t.prof is not None: t.flops, t.nbytes = ...`)"""
+
+    __slots__ = ("name", "flops", "nbytes", "ref_bytes", "prof", "e0")          # (every conv launch of an eager step passes through here)
 
     def __init__(self, name, flops=0.0, nbytes=0.0, ref_bytes=None):
         self.name, self.flops, self.nbytes, self.ref_bytes = name, flops, nbytes, ref_bytes
@@ -467,10 +470,6 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
             out = zeros((n, ohf, owf, ldy), out_dtype, x.device)
         else:
             out = torch.empty((n, ohf, owf, ldy), dtype=out_dtype, device=x.device)
-    prof = PROFILER
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
     big, mid, variant = False, -1, 0
     if tile_cfg == 0:          # the two policy functions cost ~5 us per call (the loader / consumer tile search): cached per shape
         pkey = (x.dtype, n * oh * ow, k, c, r * s * c, out_dtype, ldy % 8, BIG_TILE_POLICY, MID_TILE_POLICY)
@@ -486,31 +485,28 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
             big, variant = True, code
         else:
             mid = code
-    if mid >= 0:
-        check(lib().unit_conv2d_fwd_mid(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
-                                        n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), mid, _s()),
-              "unit_conv2d_fwd_mid")
-    elif big:
-        check(lib().unit_conv2d_fwd_big(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
-                                        n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu),
-                                        variant, _s()),
-              "unit_conv2d_fwd_big")
-    else:
-        check(lib().unit_conv2d_fwd(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(x.dtype), dt(out_dtype),
-                                    n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), tile_cfg, _s()),
-              "unit_conv2d_fwd")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        es = out.element_size()
-        nbytes = (x.numel() + w.numel()) * x.element_size() + n * oh * ow * ldy * es * (1 + (residual is not None) + (mask_ref is not None))
-        feed = None
-        if mid >= 0:          # operand bytes the busiest CU stages into LDS (feed-bound ceiling of the backbone layers, bench.py backbone_ceiling)
-            bm, bn = mid_tile_dims(mid)
-            tiles = ((n * oh * ow + bm - 1) // bm) * ((k + bn - 1) // bn)
-            feed = ((tiles + 255) // 256) * (r * s * c // 64) * (bm + bn) * 128.0
-        prof.setdefault("conv_igemm256" if (big and mid < 0) else ("conv_igemm_dma" if mid >= 0 else "conv_igemm"), []).append(
-            (e0, e1, 2.0 * n * oh * ow * k * r * s * c, nbytes, feed))
+    with _timed("conv_igemm256" if (big and mid < 0) else ("conv_igemm_dma" if mid >= 0 else "conv_igemm")) as t:
+        if mid >= 0:
+            check(lib().unit_conv2d_fwd_mid(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
+                                            n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), mid, _s()),
+                  "unit_conv2d_fwd_mid")
+        elif big:
+            check(lib().unit_conv2d_fwd_big(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
+                                            n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu),
+                                            variant, _s()),
+                  "unit_conv2d_fwd_big")
+        else:
+            check(lib().unit_conv2d_fwd(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(x.dtype), dt(out_dtype),
+                                        n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), tile_cfg, _s()),
+                  "unit_conv2d_fwd")
+        if t.prof is not None:
+            es = out.element_size()
+            t.flops = 2.0 * n * oh * ow * k * r * s * c
+            t.nbytes = (x.numel() + w.numel()) * x.element_size() + n * oh * ow * ldy * es * (1 + (residual is not None) + (mask_ref is not None))
+            if mid >= 0:          # operand bytes the busiest CU stages into LDS (feed-bound ceiling of the backbone layers, bench.py backbone_ceiling)
+                bm, bn = mid_tile_dims(mid)
+                tiles = ((n * oh * ow + bm - 1) // bm) * ((k + bn - 1) // bn)
+                t.ref_bytes = ((tiles + 255) // 256) * (r * s * c // 64) * (bm + bn) * 128.0
     return out
 
 
@@ -579,19 +575,13 @@ def conv2d_ex(x, w, k, r, s, pad=0, bias=None, residual=None, relu=False, mask_b
     if pool_rows:
         assert pool_rows == oh * ow
         part = torch.empty(lib().unit_conv_pool_partial_floats(m, ldy), dtype=torch.float32, device=x.device)
-    prof = PROFILER
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().unit_conv2d_fwd_big_ex(_p(x), _p(w), _p(y), _p(bias), _p(residual), _p(mask_bits.data if mask_bits is not None else None),
-                                       _p(bits.data if bits is not None else None), _p(part), pool_rows,
-                                       n, h, wd, c, k, r, s, pad, ldy, int(relu), _p(x2), c2, int(variant), _s()), "unit_conv2d_fwd_big_ex")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        nbytes = (x.numel() + w.numel() + (x2.numel() if x2 is not None else 0)) * 2 + m * ldy * 2 * (int(want_y) + (residual is not None)) \
-            + (m * ldy // 8) * (int(want_bits) + (mask_bits is not None))
-        prof.setdefault("conv_igemm256", []).append((e0, e1, 2.0 * m * k * r * s * (c + c2), nbytes))
+    with _timed("conv_igemm256", 2.0 * m * k * r * s * (c + c2)) as t:
+        check(lib().unit_conv2d_fwd_big_ex(_p(x), _p(w), _p(y), _p(bias), _p(residual), _p(mask_bits.data if mask_bits is not None else None),
+                                           _p(bits.data if bits is not None else None), _p(part), pool_rows,
+                                           n, h, wd, c, k, r, s, pad, ldy, int(relu), _p(x2), c2, int(variant), _s()), "unit_conv2d_fwd_big_ex")
+        if t.prof is not None:
+            t.nbytes = (x.numel() + w.numel() + (x2.numel() if x2 is not None else 0)) * 2 + m * ldy * 2 * (int(want_y) + (residual is not None)) \
+                + (m * ldy // 8) * (int(want_bits) + (mask_bits is not None))
     pooled = None
     if pool_rows:
         pooled = pooled_out if pooled_out is not None else torch.empty((n, k), dtype=x.dtype, device=x.device)
@@ -608,91 +598,70 @@ def avgpool_bwd_bits(dfeat, bits, ph, pw):
     return g
 
 
+def _fit_slab(slab, nbytes, device):
+    """the buffer a launch leaves nbytes of split-M slabs in: `slab` when it is large enough, else a new, larger one (the outgrown one
+    is retired as workspace() retires its buffers: a captured step may replay into it)"""
+    if slab is None or slab.numel() < nbytes:
+        if slab is not None:
+            _retire(slab)
+        slab = torch.empty(_grown(nbytes, slab), dtype=torch.uint8, device=device)
+    return slab
+
+
+def _wgrad_parts(x, dy, k, r, s, stride=1, pad=0):
+    """the problems of ONE layer's weight gradient, one per part: (x, dy, (n, h, w, c, oh, ow), plane passes, dtype code of the kernels).
+    x / dy: plain tensors, X3 split tensors (X3_WGRAD_PASSES passes of the bf16 kernels over their planes) or ops.Parts of either."""
+    for xp, dp in (zip(x, dy) if isinstance(x, Parts) else ((x, dy),)):
+        n, h, wd, c = xp.shape
+        oh, ow = conv_out_size(h, wd, r, s, stride, pad)
+        if type(xp) is X3:
+            yield xp, dp, (n, h, wd, c, oh, ow), X3_WGRAD_PASSES, BF16
+        else:
+            yield xp, dp, (n, h, wd, c, oh, ow), 1, dt(xp.dtype)
+
+
+def _wgrad_launch(part, k, r, s, stride, pad, ldy, out, scale, accumulate, variant, ws):
+    """one part (of _wgrad_parts) through unit_conv2d_wgrad / unit_conv2d_wgrad_x3: dw = `out` reduced from the slabs in `ws` with scale[k]
+    folded, or, out None, the slabs left there; with its profiler entry"""
+    x, dy, (n, h, wd, c, oh, ow), passes, code = part
+    with _timed("conv_wgrad", passes * 2.0 * n * oh * ow * k * r * s * c, (x.numel() + n * oh * ow * ldy) * x.element_size() + 4 * k * r * s * c):
+        if type(x) is X3:
+            assert type(dy) is X3 and x.is_contiguous() and dy.is_contiguous() and ldy == k
+            check(lib().unit_conv2d_wgrad_x3(_px(x), _px(dy), _p(out), _p(scale), n, h, wd, c, k, r, s, stride, pad, oh, ow, k, int(accumulate),
+                                             _x3v(variant), _p(ws), ws.numel(), _s()), "unit_conv2d_wgrad_x3" if out is not None else "unit_conv2d_wgrad_x3(partial)")
+        else:
+            check(lib().unit_conv2d_wgrad(_p(x), _p(dy), _p(out), _p(scale), code, n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, int(accumulate),
+                                          int(variant), _p(ws), ws.numel(), _s()), "unit_conv2d_wgrad" if out is not None else "unit_conv2d_wgrad(partial)")
+
+
 def conv2d_wgrad(x, dy, k, r, s, stride=1, pad=0, scale=None, out=None, accumulate=False, ldy=None, variant=0):
-    """x [N,H,W,C], dy [N,OH,OW,ldy] -> dw fp32 [k,r,s,C] (scale[k] folded)."""
-    if type(x) is X3:
-        assert ldy is None
-        return conv2d_wgrad_x3(x, dy, k, r, s, stride, pad, scale=scale, out=out, accumulate=accumulate, variant=variant)
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    ldy = ldy or dy.shape[-1]
+    """x [N,H,W,C], dy [N,OH,OW,ldy] -> dw fp32 [k,r,s,C] (scale[k] folded). x, dy ops.X3 (bf16x3 split tensors, ldy = k): the bf16x3
+    weight gradient."""
+    assert ldy is None or type(x) is not X3
+    part, = _wgrad_parts(x, dy, k, r, s, stride, pad)
+    n, _, _, c, oh, ow = part[2]
     if out is None:
         out = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
-    nbytes = lib().unit_conv2d_wgrad_workspace_bytes(dt(x.dtype), n, oh, ow, k, r, s, c)
+    nbytes = part[3] * lib().unit_conv2d_wgrad_workspace_bytes(part[4], n, oh, ow, k, r, s, c)
     ws = workspace(nbytes, x.device, slot=2)   # own slot: these launches may run on a side stream next to sort/NMS (slot 0)
-    prof = PROFILER
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().unit_conv2d_wgrad(_p(x), _p(dy), _p(out), _p(scale), dt(x.dtype), n, h, wd, c, k, r, s, stride, pad, oh, ow,
-                                  ldy, int(accumulate), int(variant), _p(ws), ws.numel(), _s()), "unit_conv2d_wgrad")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.setdefault("conv_wgrad", []).append((e0, e1, 2.0 * n * oh * ow * k * r * s * c,
-                                                  (x.numel() + n * oh * ow * ldy) * x.element_size() + 4 * k * r * s * c))
+    _wgrad_launch(part, k, r, s, stride, pad, ldy or dy.shape[-1], out, scale, accumulate, variant, ws)
     return out
 
 
 def conv2d_wgrad_partial(x, dy, k, r, s, stride, pad, slab=None, variant=0):
     """split-M partial slabs only (no reduction): returns (slab uint8 tensor, n_splits); slab i = floats [i*k*r*s*C, ...).
-    x / dy ops.Parts: the parts' slabs follow each other (n_splits = all of them)."""
-    if isinstance(x, Parts):
-        c = x[0].shape[-1]
-        x3 = type(x[0]) is X3
-        need, per = [], []
-        for xp, dp in zip(x, dy):
-            n, h, wd, _ = xp.shape
-            oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-            mul = X3_WGRAD_PASSES if x3 else 1
-            need.append(mul * lib().unit_conv2d_wgrad_workspace_bytes(BF16 if x3 else dt(xp.dtype), n, oh, ow, k, r, s, c))
-            per.append(mul * lib().unit_conv2d_wgrad_splits(BF16 if x3 else dt(xp.dtype), n, oh, ow, k, r, s, c))
-        nbytes = sum(need)
-        if slab is None or slab.numel() < nbytes:
-            old = slab
-            if slab is not None:
-                _retire(slab)
-            slab = torch.empty(_grown(nbytes, old), dtype=torch.uint8, device=x[0].device)
-        one = k * r * s * c * 4
-        at = 0
-        for xp, dp, sp in zip(x, dy, per):
-            n, h, wd, _ = xp.shape
-            oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-            view = slab[at * one:]
-            with _timed("conv_wgrad", (X3_WGRAD_PASSES if x3 else 1) * 2.0 * n * oh * ow * k * r * s * c, (xp.numel() + dp.numel()) * xp.element_size() + 4 * k * r * s * c):
-                if x3:
-                    check(lib().unit_conv2d_wgrad_x3(_px(xp), _px(dp), None, None, n, h, wd, c, k, r, s, stride, pad, oh, ow, k, 0, _x3v(variant), _p(view),
-                                                     view.numel(), _s()), "unit_conv2d_wgrad_x3(part)")
-                else:
-                    check(lib().unit_conv2d_wgrad(_p(xp), _p(dp), None, None, dt(xp.dtype), n, h, wd, c, k, r, s, stride, pad, oh, ow, dp.shape[-1], 0,
-                                                  int(variant), _p(view), view.numel(), _s()), "unit_conv2d_wgrad(part)")
-            at += sp
-        return slab, at
-    if type(x) is X3:
-        return _wgrad_partial_x3(x, dy, k, r, s, stride, pad, slab, variant)
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    nbytes = lib().unit_conv2d_wgrad_workspace_bytes(dt(x.dtype), n, oh, ow, k, r, s, c)
-    if slab is None or slab.numel() < nbytes:
-        old = slab
-        if slab is not None:
-            _retire(slab)       # as workspace(): a captured step may replay into the old slab
-        slab = torch.empty(_grown(nbytes, old), dtype=torch.uint8, device=x.device)
-    splits = lib().unit_conv2d_wgrad_splits(dt(x.dtype), n, oh, ow, k, r, s, c)
-    ldy = dy.shape[-1]
-    prof = PROFILER
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().unit_conv2d_wgrad(_p(x), _p(dy), None, None, dt(x.dtype), n, h, wd, c, k, r, s, stride, pad, oh, ow, dy.shape[-1], 0,
-                                  int(variant), _p(slab), slab.numel(), _s()), "unit_conv2d_wgrad(partial)")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        prof.setdefault("conv_wgrad", []).append((e0, e1, 2.0 * n * oh * ow * k * r * s * c,
-                                                  (x.numel() + n * oh * ow * ldy) * x.element_size() + 4 * k * r * s * c))
-    return slab, splits
-
+    x / dy ops.X3: passes x splits slabs; ops.Parts: the parts' slabs follow each other (n_splits = all of them)."""
+    parts = list(_wgrad_parts(x, dy, k, r, s, stride, pad))
+    c = parts[0][2][3]
+    # (a part's slabs take splits * k*r*s*C * 4 bytes: what unit_conv2d_wgrad_workspace_bytes returns)
+    per = [passes * lib().unit_conv2d_wgrad_splits(code, n, oh, ow, k, r, s, c) for _, _, (n, _, _, _, oh, ow), passes, code in parts]
+    one = k * r * s * c * 4
+    slab = _fit_slab(slab, sum(per) * one, parts[0][0].device)
+    at = 0
+    for part, sp in zip(parts, per):
+        _wgrad_launch(part, k, r, s, stride, pad, part[1].shape[-1], None, None, False, variant, slab[at * one:] if at else slab)
+        at += sp
+    return slab, at
 
 
 # ------------------------------------------------------------------------------------------------ ragged batches (two image groups)
@@ -874,23 +843,16 @@ def conv2d_x3(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref
         tile = _POLICY_CACHE.get(pkey)
         if tile is None:
             tile = _POLICY_CACHE[pkey] = X3_TILE_POLICY(m, k, c, segs * r * s * c)
-    prof = PROFILER
-    if prof is not None:
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-    check(lib().unit_conv2d_fwd_x3s(_px(x), _p(w), _px(out), _p(bias), _px(residual), _px(mask_ref), mask_c, n, h, wd, c, k, r, s, stride, pad,
-                                    oh, ow, k, oy_mul, ohf, owf, int(relu), int(tile), segs, _s()), "unit_conv2d_fwd_x3s")
-    if prof is not None:
-        e1 = torch.cuda.Event(enable_timing=True)
-        e1.record()
-        nbytes = (x.numel() + m * k * (1 + (residual is not None))) * 4 + (m * k * 2 if mask_ref is not None else 0) + w.numel() * 2
-        feed = None
-        if tile >= 0:
-            bm, bn = mid_tile_dims(tile)
-            tiles = ((m + bm - 1) // bm) * ((k + bn - 1) // bn)
-            feed = ((tiles + 255) // 256) * (segs * r * s * c // 64) * (bm + bn) * 128.0
-        # flops = the MFMA work issued: three (dgrad with two segments: two) bf16 products per fp32 product
-        prof.setdefault("conv_igemm256" if tile < 0 else "conv_igemm_dma", []).append((e0, e1, segs * 2.0 * m * k * r * s * c, nbytes, feed))
+    # flops = the MFMA work issued: three (dgrad with two segments: two) bf16 products per fp32 product
+    with _timed("conv_igemm256" if tile < 0 else "conv_igemm_dma", segs * 2.0 * m * k * r * s * c) as t:
+        check(lib().unit_conv2d_fwd_x3s(_px(x), _p(w), _px(out), _p(bias), _px(residual), _px(mask_ref), mask_c, n, h, wd, c, k, r, s, stride, pad,
+                                        oh, ow, k, oy_mul, ohf, owf, int(relu), int(tile), segs, _s()), "unit_conv2d_fwd_x3s")
+        if t.prof is not None:
+            t.nbytes = (x.numel() + m * k * (1 + (residual is not None))) * 4 + (m * k * 2 if mask_ref is not None else 0) + w.numel() * 2
+            if tile >= 0:
+                bm, bn = mid_tile_dims(tile)
+                tiles = ((m + bm - 1) // bm) * ((k + bn - 1) // bn)
+                t.ref_bytes = ((tiles + 255) // 256) * (segs * r * s * c // 64) * (bm + bn) * 128.0
     return out
 
 
@@ -920,36 +882,10 @@ def _x3v(variant):
 
 
 def conv2d_wgrad_x3(x, dy, k, r, s, stride=1, pad=0, scale=None, out=None, accumulate=False, variant=0, slab=None):
-    """bf16x3 weight gradient: x X3 [N,H,W,C], dy X3 [N,OH,OW,k] -> dw fp32 [k,r,s,C] (scale[k] folded); out=None and slab given (or
-    partial=True via conv2d_wgrad_partial): leaves the 3 * splits slabs"""
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    assert type(x) is X3 and type(dy) is X3 and x.is_contiguous() and dy.is_contiguous() and dy.shape[-1] == k
-    if out is None:
-        out = torch.empty((k, r, s, c), dtype=torch.float32, device=x.device)
-    nbytes = X3_WGRAD_PASSES * lib().unit_conv2d_wgrad_workspace_bytes(BF16, n, oh, ow, k, r, s, c)
-    ws = workspace(nbytes, x.device, slot=2)
-    with _timed("conv_wgrad", X3_WGRAD_PASSES * 2.0 * n * oh * ow * k * r * s * c, (x.numel() + dy.numel()) * 4 + 4 * k * r * s * c):
-        check(lib().unit_conv2d_wgrad_x3(_px(x), _px(dy), _p(out), _p(scale), n, h, wd, c, k, r, s, stride, pad, oh, ow, k, int(accumulate),
-                                         _x3v(variant), _p(ws), ws.numel(), _s()), "unit_conv2d_wgrad_x3")
-    return out
-
-
-def _wgrad_partial_x3(x, dy, k, r, s, stride, pad, slab, variant):
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    assert type(dy) is X3 and x.is_contiguous() and dy.is_contiguous() and dy.shape[-1] == k
-    nbytes = X3_WGRAD_PASSES * lib().unit_conv2d_wgrad_workspace_bytes(BF16, n, oh, ow, k, r, s, c)
-    if slab is None or slab.numel() < nbytes:
-        old = slab
-        if slab is not None:
-            _retire(slab)
-        slab = torch.empty(_grown(nbytes, old), dtype=torch.uint8, device=x.device)
-    splits = X3_WGRAD_PASSES * lib().unit_conv2d_wgrad_splits(BF16, n, oh, ow, k, r, s, c)
-    with _timed("conv_wgrad", X3_WGRAD_PASSES * 2.0 * n * oh * ow * k * r * s * c, (x.numel() + dy.numel()) * 4 + 4 * k * r * s * c):
-        check(lib().unit_conv2d_wgrad_x3(_px(x), _px(dy), None, None, n, h, wd, c, k, r, s, stride, pad, oh, ow, k, 0, _x3v(variant), _p(slab),
-                                         slab.numel(), _s()), "unit_conv2d_wgrad_x3(partial)")
-    return slab, splits
+    """bf16x3 weight gradient: x X3 [N,H,W,C], dy X3 [N,OH,OW,k] -> dw fp32 [k,r,s,C] (scale[k] folded); the slabs alone:
+    conv2d_wgrad_partial"""
+    assert type(x) is X3
+    return conv2d_wgrad(x, dy, k, r, s, stride, pad, scale=scale, out=out, accumulate=accumulate, variant=variant)
 
 
 class WgradProblem(ctypes.Structure):
@@ -962,13 +898,8 @@ class WgradProblem(ctypes.Structure):
 def wgrad_group_supported(x, dy, k, r, s, stride, pad):
     """may this layer's weight gradient go into a grouped launch (csrc/conv_wgrad128r.hip)? bf16 tensors, or X3 split tensors (each of
     the three plane passes of a bf16x3 weight gradient is a bf16 problem of its own in the grid); ops.Parts: every part"""
-    if isinstance(x, Parts):
-        return all(wgrad_group_supported(xp, dp, k, r, s, stride, pad) for xp, dp in zip(x, dy))
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    if type(x) is X3:
-        return type(dy) is X3 and bool(lib().unit_conv2d_wgrad_group_supported(BF16, n, oh, ow, k, r, s, c))
-    return x.dtype == torch.bfloat16 and bool(lib().unit_conv2d_wgrad_group_supported(dt(x.dtype), n, oh, ow, k, r, s, c))
+    return all((type(xp) is not X3 or type(dp) is X3) and bool(lib().unit_conv2d_wgrad_group_supported(code, n, oh, ow, k, r, s, c))
+               for xp, dp, (n, _, _, c, oh, ow), _, code in _wgrad_parts(x, dy, k, r, s, stride, pad))
 
 
 _X3_PASSES = ((0, 0), (0, 1), (1, 0))          # (plane of x, plane of dy) per pass: hi^T.hi + hi^T.lo + lo^T.hi
@@ -992,55 +923,40 @@ def conv2d_wgrad_group(items, slabs=None, splits_hint=0):
     if n_items == 0:
         return []
     assert ctypes.sizeof(WgradProblem) == lib().unit_wgrad_problem_bytes()
-    probs = []          # (item index, x part, dy part, pass | None)
+    probs = []          # (item index, x part, dy part, geometry, pass | None)
     for i, it in enumerate(items):
-        parts = list(zip(it[0], it[1])) if isinstance(it[0], Parts) else [(it[0], it[1])]
-        for xp, dp in parts:
+        for xp, dp, geo, passes, _ in _wgrad_parts(*it):
             if type(xp) is X3:
                 assert type(dp) is X3 and dp.shape[-1] == it[2]
-                probs += [(i, xp, dp, ps) for ps in range(X3_WGRAD_PASSES)]
+                probs += [(i, xp, dp, geo, ps) for ps in range(passes)]
             else:
-                probs.append((i, xp, dp, None))
+                probs.append((i, xp, dp, geo, None))
     pr = (WgradProblem * len(probs))()
     flops = nbytes = 0
-    for j, (i, x, dy, ps) in enumerate(probs):
+    one = [None] * n_items          # per item: (bytes of one slab, device)
+    for q, (i, x, dy, (n, h, wd, c, oh, ow), ps) in zip(pr, probs):
         _, _, k, r, s, stride, pad = items[i]
-        n, h, wd, c = x.shape
-        oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-        q = pr[j]
+        one[i] = (k * r * s * c * 4, x.device)
         q.N, q.H, q.W, q.C, q.K, q.R, q.S, q.stride, q.pad, q.OH, q.OW = n, h, wd, c, k, r, s, stride, pad, oh, ow
         if ps is None:
             q.x, q.dy, q.ldy = x.data_ptr(), dy.data_ptr(), dy.shape[-1]
             q.x_pitch = q.x_back = q.dy_back = 0
-            nbytes += (x.numel() + n * oh * ow * dy.shape[-1]) * 2 + 4 * k * r * s * c
         else:
             px, pd = _X3_PASSES[ps]
             q.x, q.dy, q.ldy = x.data_ptr() + px * c * 2, dy.data_ptr() + pd * k * 2, 2 * k
             q.x_pitch, q.x_back, q.dy_back = 2 * c, px * c, pd * k
-            nbytes += (x.numel() + n * oh * ow * k) * 2 + 4 * k * r * s * c
+        nbytes += (x.numel() + n * oh * ow * dy.shape[-1]) * 2 + 4 * k * r * s * c          # (X3: one bf16 plane of each operand per pass)
         flops += 2.0 * n * oh * ow * k * r * s * c
     check(lib().unit_conv2d_wgrad_group_plan(pr, len(probs), int(splits_hint)), "unit_conv2d_wgrad_group_plan")
     total = [0] * n_items
-    for j, (i, _, _, _) in enumerate(probs):
-        total[i] += pr[j].splits
-    out = []
-    for i, it in enumerate(items):
-        k, r, s = it[2], it[3], it[4]
-        x0 = it[0][0] if isinstance(it[0], Parts) else it[0]
-        one = k * r * s * x0.shape[-1] * 4
-        need = total[i] * one
-        slab = slabs[i] if slabs is not None else None
-        if slab is None or slab.numel() < need:
-            old = slab
-            if slab is not None:
-                _retire(slab)       # (conv2d_wgrad_partial)
-            slab = torch.empty(_grown(need, old), dtype=torch.uint8, device=x0.device)
-        out.append((slab, total[i]))
+    for q, p in zip(pr, probs):
+        total[p[0]] += q.splits
+    out = [(_fit_slab(slabs[i] if slabs is not None else None, total[i] * one[i][0], one[i][1]), total[i]) for i in range(n_items)]
     at = [0] * n_items
-    for j, (i, x, _, _) in enumerate(probs):
-        k, r, s = items[i][2], items[i][3], items[i][4]
-        pr[j].partial = out[i][0].data_ptr() + at[i] * k * r * s * x.shape[-1] * 4
-        at[i] += pr[j].splits
+    for q, p in zip(pr, probs):
+        i = p[0]
+        q.partial = out[i][0].data_ptr() + at[i] * one[i][0]
+        at[i] += q.splits
     with _timed("conv_wgrad", flops, nbytes):
         check(lib().unit_conv2d_wgrad_group(pr, len(probs), dt(torch.bfloat16), _s()), "unit_conv2d_wgrad_group")
     return out
