@@ -503,6 +503,28 @@ int unit_metrics_mask(const float* logits, int K, int ldk, const int* cls, const
 int unit_sgd_momentum(float* p, const float* g, float* buf, long n, float lr, float momentum, float wd, float grad_scale,
                       int first_step, const float* lr_dev, void* stream);
 
+/* ---- gradient clipping and Nesterov on the flat store (csrc/optim.hip; Detectron2 solver/build.py maybe_add_gradient_clipping) ----
+ * table: device int64 [n_seg][2] = (offset, numel) of every trainable tensor in the flat buffer, offsets ascending, rows disjoint.
+ * unit_grad_clip_coefs: for the rows [seg_lo, seg_hi): norms[r] = || g[row r] * grad_scale ||_p (norm_kind 0: inf, 1: L1, 2: L2) and
+ *   coefs[r] = min(1, clip_value / (norms[r] + 1e-6)); NaN when the norm is not finite (that tensor only); full_model != 0: every
+ *   coefs[r] of the range = the one coefficient of the p-norm over all rows of the range. Two launches for any number of rows; chunks
+ *   of unit_grad_clip_chunk() elements counted from each tensor's first element, fp64 partials combined in chunk order: the same bits
+ *   on every run, no atomics. n_chunks = sum over the range of ceil(numel / chunk) (the grid; a value that disagrees with the table
+ *   makes the whole range NaN, as does a row outside [0, g_numel) for that row). workspace: unit_grad_clip_workspace_bytes(g_numel, n_seg)
+ *   bytes, 8-byte aligned, caller-owned, no state between calls. At most 4096 rows per call.
+ * unit_sgd_step: unit_sgd_momentum on the flat range [lo, lo + n) of the buffers p, g, buf (base pointers), plus
+ *   clip_mode 0: none; 1: gs = clamp(g * grad_scale, -clip_value, clip_value) (NaN stays); 2: gs = (g * grad_scale) * coefs[row of the
+ *   element] (binary search over the table; elements of no row: 1), and nesterov != 0: p -= lr * (d + momentum * b) instead of lr * b.
+ *   g is only read. With clip_mode 0 and nesterov 0 the result is unit_sgd_momentum's bit for bit. lr_dev as above. */
+int unit_grad_clip_chunk(void);
+size_t unit_grad_clip_workspace_bytes(long g_numel, int n_seg);
+int unit_grad_clip_coefs(const float* g, long g_numel, const long* table, int n_seg, int seg_lo, int seg_hi, int n_chunks, int norm_kind,
+                         float clip_value, float grad_scale, int full_model, float* norms, float* coefs, void* workspace,
+                         size_t workspace_bytes, void* stream);
+int unit_sgd_step(float* p, const float* g, float* buf, long lo, long n, float lr, float momentum, float wd, float grad_scale,
+                  float clip_value, int first_step, int nesterov, int clip_mode, const long* table, int n_seg, const float* coefs,
+                  const float* lr_dev, void* stream);
+
 /* ---- the step's launch sequence as a call list walked in C (csrc/replay.hip; unit_amd/_lib.py Recorder, engine.ReplayedStep) ----
  * The reference's step is `loss_dict = self.model(data, ...); losses.backward(); self.optimizer.step()` (engine/defaults.py:279-284):
  * ~650 operator launches issued one by one from Python. Here the sequence of C-ABI calls of one eagerly executed step (a constant for

@@ -45,7 +45,7 @@ class Log(TorchDispatchMode):
         return func(*args, **(kwargs or {}))
 
 
-mode = sys.argv[1] if len(sys.argv) > 1 else "s1"          # s1 | two_pass | x3 | s2 | mask | eval | eval_mask
+mode = sys.argv[1] if len(sys.argv) > 1 else "s1"          # s1 | two_pass | x3 | s2 | mask | eval | eval_mask | clip (s1 with "norm" clipping + Nesterov)
 if mode in ("s2",):
     cfg = config.voc_rcnn_c4_split1_ft(101)
 elif mode in ("mask", "eval_mask"):
@@ -54,6 +54,9 @@ else:
     cfg = config.voc_rcnn_c4_split1(101)
 cfg.MODEL.DEVICE = "cuda:0"
 cfg.SEED = 0
+if mode == "clip":
+    cfg.SOLVER.NESTEROV = True
+    cfg.SOLVER.CLIP_GRADIENTS = config.CN(ENABLED=True, CLIP_TYPE="norm", CLIP_VALUE=0.05, NORM_TYPE=2.0)
 model = build_model(cfg)
 init_synthetic_weights(model, seed=1)
 model.train()

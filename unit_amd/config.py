@@ -118,6 +118,7 @@ def get_cfg():
     c.SOLVER = CN(IMS_PER_BATCH=8, BASE_LR=0.02, MOMENTUM=0.9, NESTEROV=False, WEIGHT_DECAY=1e-4, WEIGHT_DECAY_NORM=0.0,
                   WEIGHT_DECAY_BIAS=1e-4, BIAS_LR_FACTOR=1.0, STEPS=(12000, 24000), MAX_ITER=30000, WARMUP_ITERS=100,
                   WARMUP_FACTOR=1.0 / 1000, GAMMA=0.1, CHECKPOINT_PERIOD=500)
+    c.SOLVER.CLIP_GRADIENTS = CN(ENABLED=False, CLIP_TYPE="value", CLIP_VALUE=1.0, NORM_TYPE=2.0)          # "value" | "norm" | "full_model"; 1.0 | 2.0 | inf
     c.TEST = CN(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0, AUG=CN(ENABLED=False))
     c.SEED = -1
     add_config(c)

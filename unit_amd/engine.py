@@ -386,6 +386,10 @@ class TrainerNoMeta:
         weight-gradient stream and overlaps the next step's preprocessing / frozen layers (GeneralizedRCNN.overlap_optimizer_tail);
         read parameters between steps only after model.join_optimizer_tail() (state_dict() does it)."""
         self.cfg, self.model = cfg, model
+        from .solver import clip_config
+        clip = clip_config(cfg)
+        if early_update and clip is not None and clip[0] == "full_model":
+            raise ValueError('SOLVER.CLIP_GRADIENTS.CLIP_TYPE "full_model" needs every gradient before any update: not with early_update=True')
         if metrics:
             model.collect_metrics = True
         if high_priority and model.device.type == "cuda":

@@ -1615,6 +1615,49 @@ def sgd_momentum(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, first_st
                                   int(first_step), _p(lr_dev), _s()), "sgd_momentum")
 
 
+# ------------------------------------------------------------------------------------------------ gradient clipping + Nesterov (csrc/optim.hip)
+CLIP_CHUNK = 16384          # elements per chunk of unit_grad_clip_coefs (unit_grad_clip_chunk(): checked by grad_clip_workspace)
+NORM_KINDS = {float("inf"): 0, 1.0: 1, 2.0: 2}          # NORM_TYPE -> norm_kind
+CLIP_NONE, CLIP_VALUE, CLIP_COEF = 0, 1, 2          # unit_sgd_step clip_mode
+
+
+def clip_chunks(numel):
+    """how many chunks unit_grad_clip_coefs cuts a tensor of `numel` elements into"""
+    return (int(numel) + CLIP_CHUNK - 1) // CLIP_CHUNK
+
+
+def grad_clip_workspace(g_numel, n_seg, device):
+    """the caller-owned scratch of grad_clip_coefs for a gradient buffer of g_numel elements and a table of n_seg rows"""
+    assert lib().unit_grad_clip_chunk() == CLIP_CHUNK
+    return torch.empty(lib().unit_grad_clip_workspace_bytes(int(g_numel), int(n_seg)) // 8, dtype=torch.float64, device=device)
+
+
+def grad_clip_coefs(g, table, seg_lo, seg_hi, n_chunks, norm_type, clip_value, grad_scale, norms, coefs, workspace, full_model=False):
+    """norms[r] = ||g[table[r, 0] : + table[r, 1]] * grad_scale||_p and coefs[r] = min(1, clip_value / (norms[r] + 1e-6)) for the rows
+    seg_lo <= r < seg_hi of `table` (int64 [n_seg, 2] on the device: offset, numel; ascending, disjoint); full_model: one coefficient
+    from the norm over all rows of the range. n_chunks = sum(clip_chunks(numel)) over the range (the caller knows its table on the host;
+    a wrong count makes the range NaN). Two launches, bit-identical from run to run, nothing allocated."""
+    assert g.dtype == torch.float32 and g.is_contiguous() and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    assert norms.dtype == torch.float32 and coefs.dtype == torch.float32 and norms.numel() >= table.shape[0] and coefs.numel() >= table.shape[0]
+    assert norms.is_contiguous() and coefs.is_contiguous() and workspace.is_contiguous()
+    check(lib().unit_grad_clip_coefs(_p(g), g.numel(), _p(table), table.shape[0], int(seg_lo), int(seg_hi), int(n_chunks),
+                                     NORM_KINDS[float(norm_type)], float(clip_value), float(grad_scale), int(bool(full_model)), _p(norms), _p(coefs),
+                                     _p(workspace), workspace.numel() * workspace.element_size(), _s()), "grad_clip_coefs")
+
+
+def sgd_step(p, g, buf, lo, n, lr, momentum, weight_decay, grad_scale=1.0, first_step=False, lr_dev=None, nesterov=False,
+             clip_mode=CLIP_NONE, clip_value=0.0, table=None, coefs=None):
+    """sgd_momentum on the range [lo, lo + n) of the flat buffers p / g / buf, with gs = clip(g * grad_scale) (CLIP_VALUE: clamp to
+    +-clip_value; CLIP_COEF: times coefs[row of the element in `table`], 1 outside every row) and torch's Nesterov form. g is not written."""
+    assert p.dtype == g.dtype == buf.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and buf.is_contiguous()
+    assert 0 <= lo and lo + n <= min(p.numel(), g.numel(), buf.numel())
+    if clip_mode == CLIP_COEF:
+        assert table.dtype == torch.int64 and table.is_contiguous() and coefs.dtype == torch.float32 and coefs.numel() >= table.shape[0]
+    check(lib().unit_sgd_step(_p(p), _p(g), _p(buf), int(lo), int(n), float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                              float(clip_value), int(first_step), int(bool(nesterov)), int(clip_mode), _p(table),
+                              0 if table is None else table.shape[0], _p(coefs), _p(lr_dev), _s()), "sgd_step")
+
+
 # ------------------------------------------------------------------------------------------------ training metrics (csrc/metrics.hip)
 def metrics_rpn(labels, m):
     """m[0] += #(label == 1), m[1] += #(label == 0) over the sampled anchor labels (int8, any shape); m: int32 counters, zeroed by the caller"""

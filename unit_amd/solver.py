@@ -2,8 +2,26 @@
 
 FlatSGD reproduces the hyper-parameter rules of /root/reference/solver/build.py:61-114 (`build_optimizer_C4`:
 per-name LR factors REFINEMENT/MIL/DELTA, bias LR factor / weight decay) on top of torch.optim.SGD's update
-(momentum, no dampening, no nesterov), executed by the fused `unit_sgd_momentum` kernel: one launch per contiguous
-hyper-parameter segment of the flat buffer instead of one per tensor."""
+(momentum, no dampening), executed by the fused `unit_sgd_momentum` kernel: one launch per contiguous
+hyper-parameter segment of the flat buffer instead of one per tensor.
+
+The two other things `build_optimizer_C4` does are honoured as well, on the device and without a host sync (csrc/optim.hip):
+  * SOLVER.NESTEROV -- torch.optim.SGD(nesterov=True): b = momentum * b + d (first step b = d), p -= lr * (d + momentum * b);
+  * SOLVER.CLIP_GRADIENTS (Detectron2's maybe_add_gradient_clipping; a cfg without the node means disabled). The clipped quantity is
+    the true gradient g * grad_scale (data parallel: the all-reduced sum times 1 / world), before weight decay is added, as in torch.
+      "value"       clamp(g * grad_scale, -CLIP_VALUE, CLIP_VALUE) per element; a NaN stays NaN.
+      "norm"        per parameter tensor (one trainable FlatStore entry): norm = ||g * grad_scale||_p, p = NORM_TYPE in {1, 2, inf},
+                    coef = min(1, CLIP_VALUE / (norm + 1e-6)); a non-finite norm gives a NaN coefficient for that tensor only
+                    (torch's error_if_nonfinite=False); an all-zero gradient gives coef == 1.
+      "full_model"  one coefficient for all trainable tensors, from the p-norm of the per-tensor norms. It needs every gradient before
+                    any update: `step_tag` (EarlyUpdate) raises ValueError under it.
+    One deviation from torch: the flat gradient buffer (`p.grad`) is LEFT UNCLIPPED -- the clip is fused into the update
+    (`unit_sgd_step`), so the gradients are not written a second time. Padding elements of the flat buffer belong to no tensor and
+    are updated as ever (coefficient 1).
+    Under the norm types a step is one `unit_grad_clip_coefs` call per updated range (two launches for all its tensors) and then
+    `unit_sgd_step` per hyper-parameter segment. `clip_coefs()` / `grad_norms()` return the device tensors of the last step: one
+    float per trainable entry in `store.entries` order, `names` beside them; reading them involves no sync. With clipping disabled and
+    NESTEROV false the launches are exactly the `unit_sgd_momentum` calls of before."""
 import bisect
 
 import torch
@@ -27,6 +45,36 @@ def hyper_for(cfg, name):
     return (lr_mult, wd)
 
 
+CLIP_TYPES = ("value", "norm", "full_model")
+
+
+def clip_config(cfg):
+    """SOLVER.CLIP_GRADIENTS -> None (disabled, or a foreign cfg without the node) | (CLIP_TYPE, CLIP_VALUE, NORM_TYPE); an unknown
+    CLIP_TYPE or NORM_TYPE is a ValueError whether or not the node is enabled"""
+    node = getattr(cfg.SOLVER, "CLIP_GRADIENTS", None)
+    if node is None:
+        return None
+    ctype, norm = getattr(node, "CLIP_TYPE", "value"), float(getattr(node, "NORM_TYPE", 2.0))
+    if ctype not in CLIP_TYPES:
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.CLIP_TYPE must be one of {CLIP_TYPES}, got {ctype!r}")
+    if norm not in ops.NORM_KINDS:
+        raise ValueError(f"SOLVER.CLIP_GRADIENTS.NORM_TYPE must be 1.0, 2.0 or inf, got {norm!r}")
+    if not getattr(node, "ENABLED", False):
+        return None
+    return (ctype, float(getattr(node, "CLIP_VALUE", 1.0)), norm)
+
+
+def clip_table(store):
+    """the trainable entries of a FlatStore as ([names], [(offset, numel)]) in `store.entries` order = ascending offsets, disjoint: the rows
+    of the table the clipping kernels take"""
+    ents = [e for e in store.entries if e["param"].requires_grad]
+    rows = [(int(e["offset"]), int(e["numel"])) for e in ents]
+    for (o0, n0), (o1, _) in zip(rows, rows[1:]):
+        assert o0 + n0 <= o1, "FlatStore entries overlap or are out of order"
+    assert not rows or (rows[0][0] >= 0 and rows[-1][0] + rows[-1][1] <= store.size)
+    return [e["name"] for e in ents], rows
+
+
 class WarmupMultiStepLR:
     """detectron2.solver.WarmupMultiStepLR (linear warm-up) as a pure function of the iteration."""
 
@@ -47,7 +95,13 @@ class FlatSGD:
     def __init__(self, model, cfg, lr_schedule=None, grad_scale=1.0):
         self.model, self.cfg = model, cfg
         self.momentum = cfg.SOLVER.MOMENTUM
-        assert not cfg.SOLVER.NESTEROV
+        self.nesterov = bool(getattr(cfg.SOLVER, "NESTEROV", False))
+        if self.nesterov and self.momentum <= 0:
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")          # torch.optim.SGD's rule and words
+        self.clip = clip_config(cfg)          # None | (type, value, norm type)
+        self._clip_mode = ops.CLIP_NONE if self.clip is None else (ops.CLIP_VALUE if self.clip[0] == "value" else ops.CLIP_COEF)
+        self.names = None         # names of the table's rows (set with the store)
+        self._table = self._norms = self._coefs = self._clip_ws = None
         self.schedule = lr_schedule or WarmupMultiStepLR(cfg)
         self.iter = 0
         self.grad_scale = grad_scale
@@ -66,7 +120,36 @@ class FlatSGD:
             self._segments = st.segments(lambda n, p: hyper_for(self.cfg, n))
             self._buf = torch.zeros_like(st.params)
             self._first = True
+            self.names, rows = clip_table(st)
+            self._row_off = [o for o, _ in rows]
+            self._row_end = [o + n for o, n in rows]
+            self._chunk_prefix = [0]
+            for _, n in rows:
+                self._chunk_prefix.append(self._chunk_prefix[-1] + ops.clip_chunks(n))
+            if self._clip_mode == ops.CLIP_COEF:          # everything a clipped step touches is allocated here, nothing inside a step
+                dev = st.params.device
+                self._table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(dev)
+                self._norms = torch.zeros(len(rows), dtype=torch.float32, device=dev)
+                self._coefs = torch.ones(len(rows), dtype=torch.float32, device=dev)
+                self._clip_ws = ops.grad_clip_workspace(st.size, len(rows), dev)
         return st
+
+    def _rows_in(self, lo, hi):
+        """the table rows inside the flat range [lo, hi): bucket ranges (`store.tags`) and what is left between them hold whole tensors"""
+        r0, r1 = bisect.bisect_left(self._row_off, lo), bisect.bisect_left(self._row_off, hi)
+        assert (r0 == 0 or self._row_end[r0 - 1] <= lo) and (r1 == 0 or self._row_end[r1 - 1] <= hi), "an update range cuts a parameter tensor"
+        return r0, r1
+
+    def clip_coefs(self):
+        """device float32 [len(names)]: the coefficients the last step multiplied each tensor's gradient by ("norm" / "full_model"; None
+        otherwise). No sync: ordered on the current stream like `momentum_buffer()`."""
+        self.join()
+        return self._coefs
+
+    def grad_norms(self):
+        """device float32 [len(names)]: ||g * grad_scale||_p per tensor of the last step ("norm" / "full_model"; None otherwise)"""
+        self.join()
+        return self._norms
 
     def zero_grad(self, set_to_none=False):
         pass   # wgrad kernels overwrite the flat gradient buffer every step
@@ -74,11 +157,23 @@ class FlatSGD:
     def _apply(self, st, lo, hi):
         """SGD-momentum on the flat range [lo, hi), cut at the hyper-parameter segment borders (solver/build.py:85-107 groups)"""
         lr = self.schedule(self.iter) if self._lr_dev is None else 1.0
+        mode, value = self._clip_mode, (self.clip[1] if self.clip else 0.0)
+        if mode == ops.CLIP_COEF:
+            r0, r1 = self._rows_in(lo, hi)
+            if r0 < r1:
+                ops.grad_clip_coefs(st.grads, self._table, r0, r1, self._chunk_prefix[r1] - self._chunk_prefix[r0], self.clip[2], value,
+                                    self.grad_scale, self._norms, self._coefs, self._clip_ws, full_model=self.clip[0] == "full_model")
         for off, n, (lr_mult, wd) in self._segments:
             a, b = max(off, lo), min(off + n, hi)
-            if a < b:
+            if a >= b:
+                continue
+            if mode == ops.CLIP_NONE and not self.nesterov:
                 ops.sgd_momentum(st.params[a:b], st.grads[a:b], self._buf[a:b], lr * lr_mult, self.momentum, wd,
                                  self.grad_scale, first_step=self._first, lr_dev=self._lr_dev)
+            else:
+                ops.sgd_step(st.params, st.grads, self._buf, a, b - a, lr * lr_mult, self.momentum, wd, self.grad_scale,
+                             first_step=self._first, lr_dev=self._lr_dev, nesterov=self.nesterov, clip_mode=mode, clip_value=value,
+                             table=self._table, coefs=self._coefs)
 
     def use_device_lr(self, device):
         """keep the scheduled learning rate in a device float that `write_lr()` refreshes (one tiny fill launch per step)"""
@@ -91,7 +186,11 @@ class FlatSGD:
 
     def step_tag(self, tag):
         """update the parameters of one gradient bucket as soon as its gradients are final (called from the backward plan on the
-        optimizer stream); `step()` then only covers what is left. Same kernel, same arithmetic, another launch partition."""
+        optimizer stream); `step()` then only covers what is left. Same kernel, same arithmetic, another launch partition.
+        Under "norm" clipping a bucket's tensors are complete when the bucket is final (and, data parallel, all-reduced: the caller waits
+        for the bucket first), so every rank computes the same coefficients with no extra collective."""
+        if self.clip is not None and self.clip[0] == "full_model":
+            raise ValueError('CLIP_TYPE "full_model" needs every gradient before any update: no per-bucket step_tag()')
         st = self._bind()
         for t, a, b in st.tags:
             if t == tag and (a, b) not in self._early:
