@@ -15,24 +15,12 @@
 // other LDS buffer after them, one barrier per step).
 // Fused epilogue: + bias[n] (FrozenBN shift / conv bias) + residual, ReLU or ReLU-mask (dgrad), strided scatter
 // (1x1 stride-2 dgrad writes every other pixel of a pre-zeroed tensor).
-#include "common.h"
-#include "conv_epilogue.h"
-#include "conv_pair.h"
+#include "conv_fwd_host.h"
 
-struct ConvArgs {
-  const void* x; const void* w; void* y;
-  const float* bias; const void* residual; const void* mask_ref;
-  int N, H, W, C;
-  int K, R, S, stride, pad;
-  int OH, OW;
-  int ldy, oy_mul, OHf, OWf;
-  int relu;
-  int Kgemm;   // R*S*C
-  int M;       // N*OH*OW
-  int tiles_m, tiles_n;
-  unsigned x_bytes, w_bytes;
+struct ConvArgs : ConvCore {          // conv_args.h: the shared prefix, filled by conv_fwd_host.h
   ConvSecond second;  // conv_epilogue.h: pair launches
 };
+CONV_ARGS_TAIL_AT_136(ConvArgs, second);
 
 template <typename T> struct ElemsPerChunk { static constexpr int v = 16 / sizeof(T); };
 
@@ -49,29 +37,6 @@ template <> struct Mma<float> {
     f32x4 af = __builtin_bit_cast(f32x4, a), bf = __builtin_bit_cast(f32x4, b);
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i], bf[i], acc, 0, 0, 0);
-  }
-};
-
-template <typename TO> struct Out4;
-template <> struct Out4<float> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) {
-    f32x4 a = *reinterpret_cast<const f32x4*>(p); v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3];
-  }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) {
-    f32x4 a = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(p) = a;
-  }
-};
-template <> struct Out4<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
-    bf16x4 a = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)a[i];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-    bf16x4 a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = a;
   }
 };
 
@@ -232,20 +197,8 @@ static int launch_conv(ConvArgs& a, hipStream_t st) {
   constexpr int BM = 2 * TM * 16, BN = 2 * TN * 16;
   a.tiles_m = cdiv(a.M, BM); a.tiles_n = cdiv(a.K, BN);
   size_t lds = (size_t)(BM + BN) * 128 * 2;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<TI, TO, TM, TN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)conv_igemm_kernel<TI, TO, TM, TN, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  if (a.second.on) {          // pair launch: the second problem's tiles follow the first's
-    a.second.tiles_m = cdiv(a.second.M, BM);
-    a.second.tiles0 = a.tiles_m * a.tiles_n;
-    conv_igemm_kernel<TI, TO, TM, TN, true><<<(a.tiles_m + a.second.tiles_m) * a.tiles_n, 256, lds, st>>>(a);
-  } else
-  conv_igemm_kernel<TI, TO, TM, TN><<<a.tiles_m * a.tiles_n, 256, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  if (a.second.on) return conv_launch<conv_igemm_kernel<TI, TO, TM, TN, true>, conv_igemm_kernel<TI, TO, TM, TN>>(pair_grid(a, BM), 256, lds, a, st);
+  return conv_launch<conv_igemm_kernel<TI, TO, TM, TN>, conv_igemm_kernel<TI, TO, TM, TN, true>>(a.tiles_m * a.tiles_n, 256, lds, a, st);
 }
 
 template <typename TI, typename TO>
@@ -281,22 +234,12 @@ extern "C" int unit_conv2d_fwd(const void* x, const void* w, void* y, const floa
 int unit_conv_generic_impl(const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref, int in_dtype,
                            int out_dtype, int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy, int oy_mul,
                            int OHf, int OWf, int relu, int tile_cfg, const UnitConvSecond* second, void* stream) {
-  int epc = in_dtype == UNIT_BF16 ? 8 : 4;
-  UNIT_CHECK_ARG(C % epc == 0, "conv: C must be a multiple of 8 (bf16) / 4 (fp32)");
-  UNIT_CHECK_ARG(ldy % 4 == 0 && ldy >= K, "conv: ldy must be a multiple of 4 and >= K");
-  UNIT_CHECK_ARG(OH == (H + 2 * pad - R) / stride + 1 && OW == (W + 2 * pad - S) / stride + 1, "conv: OH/OW mismatch");
-  UNIT_CHECK_ARG((OH - 1) * oy_mul < OHf && (OW - 1) * oy_mul < OWf, "conv: output scatter out of range");
-  UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0), "conv: 16B alignment");
+  size_t esz = in_dtype == UNIT_BF16 ? 2 : 4;          // a 16-byte chunk of k per lane: 8 bf16 / 4 fp32
   ConvArgs a;
-  a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = mask_ref;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-  a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = oy_mul; a.OHf = OHf; a.OWf = OWf; a.relu = relu;
-  a.Kgemm = R * S * C; a.M = N * OH * OW;
-  size_t esz = in_dtype == UNIT_BF16 ? 2 : 4;
-  size_t xb = (size_t)N * H * W * C * esz, wb = (size_t)K * R * S * C * esz;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull, "conv: operand larger than 4 GiB (32-bit buffer offsets)");
-  a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-  { int rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * esz); if (rc != UNIT_OK) return rc; }
+  int rc = conv_core_fill(a, CONV_RULES("conv", (int)(16 / esz), "8 (bf16) / 4 (fp32)", 4, " (32-bit buffer offsets)"), x, w, y, bias, residual, mask_ref,
+                          N, H, W, C, K, R, S, stride, pad, OH, OW, ldy, oy_mul, OHf, OWf, relu, (size_t)C * esz, C, esz);
+  if (rc == UNIT_OK) rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * esz);
+  if (rc != UNIT_OK) return rc;
   if (K == 0 || (a.M == 0 && !a.second.on)) return UNIT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (in_dtype == UNIT_BF16 && out_dtype == UNIT_BF16) return dispatch_tile<bf16_t, bf16_t>(a, tile_cfg, st);

@@ -17,28 +17,9 @@
 #endif
 
 #include "conv_igemm128.h"
-#include "conv_pair.h"
+#include "conv_fwd_host.h"
 
 __device__ __forceinline__ int swz128(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-
-template <typename TO> struct Out4;
-template <> struct Out4<float> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) { f32x4 a = *reinterpret_cast<const f32x4*>(p); v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { f32x4 a = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(p) = a; }
-};
-template <> struct Out4<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
-    bf16x4 a = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)a[i];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-    bf16x4 a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = a;
-  }
-};
 
 typedef __attribute__((address_space(3))) void lds_void_t;
 
@@ -439,35 +420,29 @@ __global__ void __launch_bounds__(512, 2) conv_igemm_dma_ksplit_kernel(ConvDmaAr
 template <typename TO>
 static int launch_ksplit(ConvDmaArgs& a, hipStream_t st) {
   a.tiles_m = cdiv(a.M, 128); a.tiles_n = cdiv(a.K, 128);
-  size_t lds = 4 * (128 + 128) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_dma_ksplit_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm_dma_ksplit_kernel<TO><<<a.tiles_m * a.tiles_n, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm_dma_ksplit_kernel<TO>>(a.tiles_m * a.tiles_n, 512, 4 * (128 + 128) * 128, a, st);
 }
 
 template <typename TO, int BM, int BN, int NS, bool X3 = false>
 static int launch_dma(ConvDmaArgs& a, hipStream_t st) {
   a.tiles_m = cdiv(a.M, BM); a.tiles_n = cdiv(a.K, BN);
   size_t lds = (size_t)NS * (BM + BN) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<TO, BM, BN, NS, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)conv_igemm_dma_kernel<TO, BM, BN, NS, X3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
+  if (a.second.on)
+    return conv_launch<conv_igemm_dma_kernel<TO, BM, BN, NS, X3, true>, conv_igemm_dma_kernel<TO, BM, BN, NS, X3>>(pair_grid(a, BM), 256, lds, a, st);
+  return conv_launch<conv_igemm_dma_kernel<TO, BM, BN, NS, X3>, conv_igemm_dma_kernel<TO, BM, BN, NS, X3, true>>(a.tiles_m * a.tiles_n, 256, lds, a, st);
+}
+
+// tile 0..5 of unit_conv2d_fwd_mid for an output type
+template <typename TO>
+static int launch_mid_tile(ConvDmaArgs& a, int tile, hipStream_t st) {
+  switch (tile) {
+    case 3: return launch_ksplit<TO>(a, st);
+    case 0: return launch_dma<TO, 128, 128, 2>(a, st);
+    case 1: return launch_dma<TO, 64, 128, 3>(a, st);
+    case 4: return launch_dma<TO, 96, 128, 3>(a, st);      // 100 x 2 workgroups on the res4 1x1 -> 256 layers: one round, one per CU
+    case 5: return launch_dma<TO, 96, 128, 2>(a, st);
+    default: return launch_dma<TO, 128, 64, 3>(a, st);
   }
-  if (a.second.on) {          // pair launch (conv_epilogue.h ConvSecond): the second problem's tiles follow the first's
-    a.second.tiles_m = cdiv(a.second.M, BM);
-    a.second.tiles0 = a.tiles_m * a.tiles_n;
-    conv_igemm_dma_kernel<TO, BM, BN, NS, X3, true><<<(a.tiles_m + a.second.tiles_m) * a.tiles_n, 256, lds, st>>>(a);
-  } else
-  conv_igemm_dma_kernel<TO, BM, BN, NS, X3><<<a.tiles_m * a.tiles_n, 256, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
 }
 
 // bf16x3 operands (unit_conv2d_fwd_x3, conv_igemm256.hip fills the argument block): tile 0 = 128x128, 1 = 64x128, 2 = 128x64 of the
@@ -494,42 +469,20 @@ extern "C" int unit_conv2d_fwd_mid(const void* x, const void* w, void* y, const 
 int unit_conv_mid_impl(const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref, int out_dtype, int N,
                        int H, int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy, int oy_mul, int OHf, int OWf, int relu,
                        int tile, const UnitConvSecond* second, void* stream) {
-  UNIT_CHECK_ARG(C % 64 == 0, "conv_mid: C must be a multiple of 64");
-  UNIT_CHECK_ARG(ldy % 4 == 0 && ldy >= K, "conv_mid: ldy must be a multiple of 4 and >= K");
-  UNIT_CHECK_ARG(OH == (H + 2 * pad - R) / stride + 1 && OW == (W + 2 * pad - S) / stride + 1, "conv_mid: OH/OW mismatch");
-  UNIT_CHECK_ARG((OH - 1) * oy_mul < OHf && (OW - 1) * oy_mul < OWf, "conv_mid: output scatter out of range");
-  UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0), "conv_mid: 16B alignment");
-  UNIT_CHECK_ARG((tile >= 0 && tile <= 5) || tile >= 100, "conv_mid: tile must be 0..5 or a loader / consumer tile code (>= 100)");
   ConvDmaArgs a;
-  a.sk = SplitK{0, 0, 0, 0}; a.mask_pitch = 0; a.second.on = 0;
-  a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = mask_ref;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-  a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = oy_mul; a.OHf = OHf; a.OWf = OWf; a.relu = relu;
-  a.Kgemm = R * S * C; a.M = N * OH * OW;
-  size_t xb = (size_t)N * H * W * C * 2, wb = (size_t)K * R * S * C * 2;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull, "conv_mid: operand larger than 4 GiB");
-  a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-  { int rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * 2); if (rc != UNIT_OK) return rc; }
+  int rc = conv_core_fill(a, CONV_RULES("conv_mid", 64, "64", 4, ""), x, w, y, bias, residual, mask_ref, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy,
+                          oy_mul, OHf, OWf, relu, (size_t)C * 2, C, 2);
+  if (rc != UNIT_OK) return rc;
+  UNIT_CHECK_ARG((tile >= 0 && tile <= 5) || tile >= 100, "conv_mid: tile must be 0..5 or a loader / consumer tile code (>= 100)");
+  a.sk = SplitK{0, 0, 0, 0}; a.mask_pitch = 0;
+  rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * 2);
+  if (rc != UNIT_OK) return rc;
   if (K == 0 || (a.M == 0 && !a.second.on)) return UNIT_OK;
   UNIT_CHECK_ARG(!a.second.on || tile != 3, "conv_mid: the split-K tile has no pair form");
   hipStream_t st = (hipStream_t)stream;
   if (tile >= 100) return unit_conv_lc_launch(a, out_dtype, tile, st);       // persistent loader / consumer workgroups (conv_igemm_lc.hip)
-  if (out_dtype == UNIT_BF16) {
-    if (tile == 3) return launch_ksplit<bf16_t>(a, st);
-    if (tile == 0) return launch_dma<bf16_t, 128, 128, 2>(a, st);
-    if (tile == 1) return launch_dma<bf16_t, 64, 128, 3>(a, st);
-    if (tile == 4) return launch_dma<bf16_t, 96, 128, 3>(a, st);      // 100 x 2 workgroups on the res4 1x1 -> 256 layers: one round, one per CU
-    if (tile == 5) return launch_dma<bf16_t, 96, 128, 2>(a, st);
-    return launch_dma<bf16_t, 128, 64, 3>(a, st);
-  }
-  if (out_dtype == UNIT_F32) {
-    if (tile == 3) return launch_ksplit<float>(a, st);
-    if (tile == 0) return launch_dma<float, 128, 128, 2>(a, st);
-    if (tile == 1) return launch_dma<float, 64, 128, 3>(a, st);
-    if (tile == 4) return launch_dma<float, 96, 128, 3>(a, st);
-    if (tile == 5) return launch_dma<float, 96, 128, 2>(a, st);
-    return launch_dma<float, 128, 64, 3>(a, st);
-  }
+  if (out_dtype == UNIT_BF16) return launch_mid_tile<bf16_t>(a, tile, st);
+  if (out_dtype == UNIT_F32) return launch_mid_tile<float>(a, tile, st);
   unit_set_error("conv_mid: unsupported out dtype");
   return UNIT_ERR_UNSUPPORTED;
 }

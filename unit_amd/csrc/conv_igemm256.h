@@ -1,21 +1,10 @@
 // conv_igemm256.h -- argument block and LDS layout helpers shared by the 256x256-tile implicit-GEMM conv kernels
-// (conv_igemm256.hip: 8-wave kernels; conv_igemm256p8.hip: phase-interleaved schedule with counted vmcnt).
+// (conv_igemm256.hip: 8-wave kernels; conv_igemm256p8.hip: phase-interleaved schedule with counted vmcnt). The block is the shared prefix of
+// conv_args.h, filled by conv_fwd_host.h (conv_core_fill), and the tail below, whose defaults are conv_fwd_host.h's conv256_defaults.
 #pragma once
-#include "common.h"
+#include "conv_args.h"
 
-#include "conv_epilogue.h"
-
-struct Conv256Args {
-  const void* x; const void* w; void* y;
-  const float* bias; const void* residual; const void* mask_ref;
-  int N, H, W, C;
-  int K, R, S, stride, pad;
-  int OH, OW;
-  int ldy, oy_mul, OHf, OWf;
-  int relu;
-  int Kgemm, M;
-  int tiles_m, tiles_n;
-  unsigned x_bytes, w_bytes;
+struct Conv256Args : ConvCore {
   EpiExtra ex;      // conv_epilogue.h; all-null unless launched through unit_conv2d_fwd_big_ex
   int ex_on;
   // second input tensor of a 1x1 conv (conv_igemm256p8.hip only): k-tiles >= cb_split read x2 [M][ratio2 * cb_split * 64] -- the
@@ -34,31 +23,13 @@ struct Conv256Args {
   SplitK sk;         // conv_epilogue.h: bf16x3 operands (X3 kernel instantiations only; nseg == 0 otherwise)
   int mask_pitch;    // split epilogue: elements per row of mask_ref
 };
+CONV_ARGS_TAIL_AT_136(Conv256Args, ex);
 
 // LDS image of an operand stage: [row][128 B = 64 k]; 16-B chunks XOR-swizzled with (row>>1)&7 (applied to the SOURCE
 // chunk of the lane-linear LDS-DMA, undone here by the fragment reads)
 __device__ __forceinline__ int swz256(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
 
 typedef __attribute__((address_space(3))) void lds_void;
-
-template <typename TO> struct O4;
-template <> struct O4<float> {
-  static __device__ __forceinline__ void load(const float* p, float (&v)[4]) { f32x4 a = *reinterpret_cast<const f32x4*>(p); v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; }
-  static __device__ __forceinline__ void store(float* p, const float (&v)[4]) { f32x4 a = {v[0], v[1], v[2], v[3]}; *reinterpret_cast<f32x4*>(p) = a; }
-};
-template <> struct O4<bf16_t> {
-  static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[4]) {
-    bf16x4 a = *reinterpret_cast<const bf16x4*>(p);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) v[i] = (float)a[i];
-  }
-  static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[4]) {
-    bf16x4 a;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) a[i] = (bf16_t)v[i];
-    *reinterpret_cast<bf16x4*>(p) = a;
-  }
-};
 
 // conv_igemm256p8.hip: the 8-phase (4 per k-tile) schedule of the same tile
 int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st);

@@ -9,7 +9,7 @@
 // while k-tile t is multiplied; one vmcnt(0)+barrier per k-tile.  Requires C % 64 == 0 (every layer except the stem).
 #include "conv_igemm256.h"
 #include "conv_igemm128.h"
-#include "conv_pair.h"
+#include "conv_fwd_host.h"
 #include "conv_epilogue.h"
 
 // diagnostic builds only (tools/exp256.sh): 1 = no operand DMA after the first k-tile (MFMA + LDS-read bound of the loop),
@@ -209,7 +209,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_kernel(Conv256Args p) {
         for (int j = 0; j < 4; ++j) v[j] += (n + j < p.K) ? p.bias[n + j] : 0.f;
       }
       if (Rz) {
-        float rr[4]; O4<TO>::load(Rz + off + n, rr);
+        float rr[4]; Out4<TO>::load(Rz + off + n, rr);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] += rr[j];
       }
@@ -218,11 +218,11 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_kernel(Conv256Args p) {
         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
       }
       if (Mk) {
-        float mm[4]; O4<TO>::load(Mk + off + n, mm);
+        float mm[4]; Out4<TO>::load(Mk + off + n, mm);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = mm[j] > 0.f ? v[j] : 0.f;
       }
-      O4<TO>::store(Y + off + n, v);
+      Out4<TO>::store(Y + off + n, v);
     }
   }
 }
@@ -371,15 +371,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_halo7_kernel(Conv256Args
 
 static int launch256_halo7(Conv256Args& a, hipStream_t st) {
   a.tiles_m = cdiv(a.M, 256); a.tiles_n = cdiv(a.K, 256);
-  size_t lds = 2 * (272 + 1) * 128 + 2 * 256 * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm256_halo7_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm256_halo7_kernel<<<a.tiles_m * a.tiles_n, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm256_halo7_kernel>(a.tiles_m * a.tiles_n, 512, 2 * (272 + 1) * 128 + 2 * 256 * 128, a, st);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -533,7 +525,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_k32_kernel(Conv256Args p
         for (int j = 0; j < 4; ++j) v[j] += (n + j < p.K) ? p.bias[n + j] : 0.f;
       }
       if (Rz) {
-        float rr[4]; O4<TO>::load(Rz + off + n, rr);
+        float rr[4]; Out4<TO>::load(Rz + off + n, rr);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] += rr[j];
       }
@@ -542,11 +534,11 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_k32_kernel(Conv256Args p
         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
       }
       if (Mk) {
-        float mm[4]; O4<TO>::load(Mk + off + n, mm);
+        float mm[4]; Out4<TO>::load(Mk + off + n, mm);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = mm[j] > 0.f ? v[j] : 0.f;
       }
-      O4<TO>::store(Y + off + n, v);
+      Out4<TO>::store(Y + off + n, v);
     }
   }
 }
@@ -554,36 +546,13 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_k32_kernel(Conv256Args p
 template <typename TO>
 static int launch256_k32(Conv256Args& a, hipStream_t st) {
   a.tiles_m = cdiv(a.M, 256); a.tiles_n = cdiv(a.K, 256);
-  size_t lds = 4 * (256 + 256) * 64;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm256_k32_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm256_k32_kernel<TO><<<a.tiles_m * a.tiles_n, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm256_k32_kernel<TO>>(a.tiles_m * a.tiles_n, 512, 4 * (256 + 256) * 64, a, st);
 }
 
 template <typename TO, bool PP, int FB>
 static int launch256(Conv256Args& a, hipStream_t st) {
   a.tiles_m = cdiv(a.M, 32 * FB); a.tiles_n = cdiv(a.K, 256);
-  size_t lds = 2 * (256 + 256) * 128;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm256_kernel<TO, PP, FB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm256_kernel<TO, PP, FB><<<a.tiles_m * a.tiles_n, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
-}
-
-static void set_div_magics(Conv256Args& a) {
-  unsigned long long mx = (unsigned long long)(a.M + 512) * (unsigned long long)(a.OW > a.OH ? a.OW : a.OH);
-  bool ok = mx < 0xFFFFFFFFull;
-  a.magic_ow = ok ? div_magic((unsigned)a.OW) : 0u;
-  a.magic_oh = ok ? div_magic((unsigned)a.OH) : 0u;
+  return conv_launch<conv_igemm256_kernel<TO, PP, FB>>(a.tiles_m * a.tiles_n, 512, 2 * (256 + 256) * 128, a, st);
 }
 
 // Position classes of a 3x3 s1 p1 "same" conv (Conv256Args::pm_cls): the map rows split into runs with the same in-map tap rows
@@ -636,24 +605,13 @@ extern "C" int unit_conv2d_fwd_big(const void* x, const void* w, void* y, const 
 int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref, int out_dtype, int N,
                        int H, int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy, int oy_mul, int OHf, int OWf, int relu,
                        int variant, const UnitConvSecond* second, void* stream) {
-  UNIT_CHECK_ARG(C % 64 == 0, "conv_big: C must be a multiple of 64");
-  UNIT_CHECK_ARG(ldy % 4 == 0 && ldy >= K, "conv_big: ldy must be a multiple of 4 and >= K");
-  UNIT_CHECK_ARG(OH == (H + 2 * pad - R) / stride + 1 && OW == (W + 2 * pad - S) / stride + 1, "conv_big: OH/OW mismatch");
-  UNIT_CHECK_ARG((OH - 1) * oy_mul < OHf && (OW - 1) * oy_mul < OWf, "conv_big: output scatter out of range");
-  UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0), "conv_big: 16B alignment");
   Conv256Args a;
-  a.sk = SplitK{0, 0, 0, 0}; a.mask_pitch = 0; a.second.on = 0;
-  a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = mask_ref;
-  a.N = N; a.H = H; a.W = W; a.C = C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-  a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = oy_mul; a.OHf = OHf; a.OWf = OWf; a.relu = relu;
-  a.Kgemm = R * S * C; a.M = N * OH * OW;
-  size_t xb = (size_t)N * H * W * C * 2, wb = (size_t)K * R * S * C * 2;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull, "conv_big: operand larger than 4 GiB");
-  a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-  a.ex = EpiExtra{nullptr, nullptr, nullptr, 0}; a.ex_on = 0;
-  a.x2 = nullptr; a.x2_bytes = 0; a.cb_split = 0; a.ratio2 = 1; a.pm_ncls = 0;
-  set_div_magics(a);
-  { int rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * 2); if (rc != UNIT_OK) return rc; }
+  int rc = conv_core_fill(a, CONV_RULES("conv_big", 64, "64", 4, ""), x, w, y, bias, residual, mask_ref, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy,
+                          oy_mul, OHf, OWf, relu, (size_t)C * 2, C, 2);
+  if (rc != UNIT_OK) return rc;
+  conv256_defaults(a);
+  rc = unit_fill_second(a.second, second, R, S, stride, pad, oy_mul, (size_t)C * 2);
+  if (rc != UNIT_OK) return rc;
   if (K == 0 || (a.M == 0 && !a.second.on)) return UNIT_OK;
   hipStream_t st = (hipStream_t)stream;
   if (variant == 0) variant = 8;          // the production kernel; everything below decodes an explicit variant
@@ -686,9 +644,7 @@ int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias,
     bool r224 = variant == 9 || (variant == 10 && fewer_with_224());
     // position-class tiles (Conv256Args::pm_ncls): 3x3 s1 p1 conv on a small map, plain bf16 output, when skipping the all-padding
     // taps saves more k-tiles than padding every class to whole tiles costs
-    if (variant == 8 && out_dtype == UNIT_BF16 && (ldy & 7) == 0 && R == 3 && S == 3 && stride == 1 &&
-        pad == 1 && OH == H && OW == W && oy_mul == 1 && OHf == OH && OWf == OW && H * W <= 4096 && (size_t)N * H * W * ldy * 2 < 0xFFFFFFF0ull)
-      build_position_classes(a);
+    if (variant == 8 && out_dtype == UNIT_BF16 && (ldy & 7) == 0 && conv_position_classes_apply(a, 2)) build_position_classes(a);
     return unit_conv256_p8_launch(a, out_dtype, variant >= 8, r224, st);
   }
   // the two-stage kernels. 4 (and any other number): one barrier per k-tile, 256-row tiles; 3: 224-row tiles; 5: 224 or 256 rows per launch;
@@ -739,46 +695,30 @@ extern "C" int unit_conv2d_fwd_x3s(const void* x, const void* w, void* y, const 
 int unit_conv_x3_impl(const void* x, const void* w, void* y, const float* bias, const void* residual, const void* mask_ref, int mask_c, int N, int H,
                       int W, int C, int K, int R, int S, int stride, int pad, int OH, int OW, int ldy, int oy_mul, int OHf, int OWf, int relu, int tile,
                       const UnitConvSecond* second, void* stream, int segs) {
-  UNIT_CHECK_ARG(C % 64 == 0, "conv_x3: C must be a multiple of 64");
-  UNIT_CHECK_ARG(ldy % 8 == 0 && ldy >= K, "conv_x3: ldy must be a multiple of 8 and >= K");
-  UNIT_CHECK_ARG(OH == (H + 2 * pad - R) / stride + 1 && OW == (W + 2 * pad - S) / stride + 1, "conv_x3: OH/OW mismatch");
-  UNIT_CHECK_ARG((OH - 1) * oy_mul < OHf && (OW - 1) * oy_mul < OWf, "conv_x3: output scatter out of range");
-  UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0), "conv_x3: 16B alignment");
+  // the kernels see segs * C virtual channels of a split x with 4 bytes per real channel and pixel
+  ConvCore core;
+  int rc = conv_core_fill(core, CONV_RULES("conv_x3", 64, "64", 8, ""), x, w, y, bias, residual, mask_ref, N, H, W, C, K, R, S, stride, pad, OH, OW, ldy,
+                          oy_mul, OHf, OWf, relu, (size_t)C * 4, segs * C, 2);
+  if (rc != UNIT_OK) return rc;
   UNIT_CHECK_ARG(mask_ref == nullptr || (mask_c >= ldy && mask_c % 8 == 0), "conv_x3: mask_c must be the mask tensor's channels per plane");
-  const int NSEG = segs;
-  size_t xb = (size_t)N * H * W * C * 4, wb = (size_t)K * R * S * C * NSEG * 2;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull, "conv_x3: operand larger than 4 GiB");
-  SplitK sk{NSEG, NSEG == 3 ? 0x1 : 0x0, C, 2 * C};          // segments [lo.Wh, hi.Wh, hi.Wl] | [hi.Wh, hi.Wl]
+  SplitK sk{segs, segs == 3 ? 0x1 : 0x0, C, 2 * C};          // segments [lo.Wh, hi.Wh, hi.Wl] | [hi.Wh, hi.Wl]
   hipStream_t st = (hipStream_t)stream;
   ConvSecond sec;
-  { int rc = unit_fill_second(sec, second, R, S, stride, pad, oy_mul, (size_t)C * 4); if (rc != UNIT_OK) return rc; }
-  if (K == 0 || ((long)N * OH * OW == 0 && !sec.on)) return UNIT_OK;
+  rc = unit_fill_second(sec, second, R, S, stride, pad, oy_mul, (size_t)C * 4);
+  if (rc != UNIT_OK) return rc;
+  if (K == 0 || (core.M == 0 && !sec.on)) return UNIT_OK;
   if (tile >= 0) {
     ConvDmaArgs a;
-    a.second = sec;
-    a.sk = sk; a.mask_pitch = 2 * mask_c;
-    a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = mask_ref;
-    a.N = N; a.H = H; a.W = W; a.C = NSEG * C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-    a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = oy_mul; a.OHf = OHf; a.OWf = OWf; a.relu = relu;
-    a.Kgemm = R * S * NSEG * C; a.M = N * OH * OW;
-    a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
+    static_cast<ConvCore&>(a) = core;
+    a.second = sec; a.sk = sk; a.mask_pitch = 2 * mask_c;
     return unit_conv_mid_x3_launch(a, tile, st);
   }
   Conv256Args a;
-  a.second = sec;
-  a.sk = sk; a.mask_pitch = 2 * mask_c;
-  a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = mask_ref;
-  a.N = N; a.H = H; a.W = W; a.C = NSEG * C; a.K = K; a.R = R; a.S = S; a.stride = stride; a.pad = pad;
-  a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = oy_mul; a.OHf = OHf; a.OWf = OWf; a.relu = relu;
-  a.Kgemm = R * S * NSEG * C; a.M = N * OH * OW;
-  a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-  a.ex = EpiExtra{nullptr, nullptr, nullptr, 0}; a.ex_on = 0;
-  a.x2 = nullptr; a.x2_bytes = 0; a.cb_split = 0; a.ratio2 = 1; a.pm_ncls = 0;
-  set_div_magics(a);
+  static_cast<ConvCore&>(a) = core;
+  conv256_defaults(a);
+  a.second = sec; a.sk = sk; a.mask_pitch = 2 * mask_c;
   // position-class tiles (3x3 s1 p1 on a small map: the k-tiles of all-padding taps are skipped) as in unit_conv2d_fwd_big
-  if (!sec.on && R == 3 && S == 3 && stride == 1 && pad == 1 && OH == H && OW == W && oy_mul == 1 && OHf == OH && OWf == OW && H * W <= 4096 &&
-      (size_t)N * H * W * ldy * 4 < 0xFFFFFFF0ull)
-    build_position_classes(a);
+  if (!sec.on && conv_position_classes_apply(a, 4)) build_position_classes(a);
   return unit_conv256_p8_launch(a, UNIT_BF16, true, false, st);
 }
 
@@ -824,26 +764,20 @@ extern "C" int unit_conv2d_fwd_big_ex(const void* x, const void* w, void* y, con
   // w = [K][C + C2]. C2 must be a multiple of C.
   UNIT_CHECK_ARG(x2 == nullptr || (R == 1 && S == 1 && pad == 0 && C2 > 0 && C2 % C == 0 && ((uintptr_t)x2 % 16 == 0)),
                  "conv_big_ex: a second input needs a 1x1 conv and C2 a multiple of C");
-  UNIT_CHECK_ARG(C % 64 == 0 && (x2 == nullptr || C2 % 64 == 0), "conv_big_ex: C must be a multiple of 64");
-  UNIT_CHECK_ARG(ldy % 8 == 0 && ldy >= K, "conv_big_ex: ldy must be a multiple of 8 and >= K");
+  UNIT_CHECK_ARG(x2 == nullptr || C2 % 64 == 0, "conv_big_ex: C must be a multiple of 64");
   UNIT_CHECK_ARG(y != nullptr || pool_partial != nullptr, "conv_big_ex: no output requested");
-  UNIT_CHECK_ARG((mask_bits == nullptr && relu_bits == nullptr) || ldy % 64 == 0, "conv_big_ex: bit masks need ldy % 64 == 0");
   UNIT_CHECK_ARG(pool_partial == nullptr || pool_rows >= 44, "conv_big_ex: a 128-row wave tile must span at most 4 pooling segments");
-  UNIT_CHECK_ARG(((uintptr_t)x % 16 == 0) && ((uintptr_t)w % 16 == 0) && ((uintptr_t)y % 16 == 0), "conv_big_ex: 16B alignment");
   int OH = H + 2 * pad - R + 1, OW = W + 2 * pad - S + 1;
   UNIT_CHECK_ARG(OH > 0 && OW > 0, "conv_big_ex: empty output");
-  Conv256Args a;
-  a.sk = SplitK{0, 0, 0, 0}; a.mask_pitch = 0; a.second.on = 0;
-  a.x = x; a.w = w; a.y = y; a.bias = bias; a.residual = residual; a.mask_ref = nullptr;
-  const int Ct = C + (x2 ? C2 : 0);
-  a.N = N; a.H = H; a.W = W; a.C = Ct; a.K = K; a.R = R; a.S = S; a.stride = 1; a.pad = pad;
-  a.OH = OH; a.OW = OW; a.ldy = ldy; a.oy_mul = 1; a.OHf = OH; a.OWf = OW; a.relu = relu;
-  a.Kgemm = R * S * Ct; a.M = N * OH * OW;
-  size_t xb = (size_t)N * H * W * C * 2, wb = (size_t)K * R * S * Ct * 2, x2b = x2 ? (size_t)N * H * W * C2 * 2 : 0;
-  UNIT_CHECK_ARG(xb < 0xFFFFFFF0ull && wb < 0xFFFFFFF0ull && x2b < 0xFFFFFFF0ull, "conv_big_ex: operand larger than 4 GiB");
-  a.x_bytes = (unsigned)xb; a.w_bytes = (unsigned)wb;
-  a.x2 = x2; a.x2_bytes = (unsigned)x2b; a.cb_split = C / 64; a.ratio2 = x2 ? C2 / C : 1; a.pm_ncls = 0;
-  set_div_magics(a);
+  Conv256Args a;          // a stride-1 conv with a plain output over C + C2 channels
+  int rc = conv_core_fill(a, CONV_RULES("conv_big_ex", 64, "64", 8, ""), x, w, y, bias, residual, nullptr, N, H, W, C, K, R, S, 1, pad, OH, OW, ldy, 1, OH, OW,
+                          relu, (size_t)C * 2, C + (x2 ? C2 : 0), 2);
+  if (rc != UNIT_OK) return rc;
+  UNIT_CHECK_ARG((mask_bits == nullptr && relu_bits == nullptr) || ldy % 64 == 0, "conv_big_ex: bit masks need ldy % 64 == 0");
+  size_t x2b = x2 ? (size_t)N * H * W * C2 * 2 : 0;
+  UNIT_CHECK_ARG(x2b < 0xFFFFFFF0ull, "conv_big_ex: operand larger than 4 GiB");
+  conv256_defaults(a);
+  a.x2 = x2; a.x2_bytes = (unsigned)x2b; a.cb_split = C / 64; a.ratio2 = x2 ? C2 / C : 1;
   a.ex = EpiExtra{relu_bits, mask_bits, pool_partial, pool_rows}; a.ex_on = 1;
   if (a.M == 0 || K == 0) return UNIT_OK;
   if (variant == 11) return unit_conv256_p8m_launch(a, UNIT_BF16, (hipStream_t)stream);

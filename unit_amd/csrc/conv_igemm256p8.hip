@@ -542,7 +542,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
         for (int j = 0; j < 4; ++j) v[j] += (n + j < p.K) ? p.bias[n + j] : 0.f;
       }
       if (Rz) {
-        float rr[4]; O4<TO>::load(Rz + off + n, rr);
+        float rr[4]; Out4<TO>::load(Rz + off + n, rr);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] += rr[j];
       }
@@ -551,11 +551,11 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
         for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
       }
       if (Mk) {
-        float mm[4]; O4<TO>::load(Mk + off + n, mm);
+        float mm[4]; Out4<TO>::load(Mk + off + n, mm);
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = mm[j] > 0.f ? v[j] : 0.f;
       }
-      O4<TO>::store(Y + off + n, v);
+      Out4<TO>::store(Y + off + n, v);
     }
   }
 }
@@ -566,17 +566,7 @@ static int launch256_p8(Conv256Args& a, hipStream_t st) {
     if constexpr (RM && B1 == 4 && sizeof(TO) == 2) {
       a.pm_ncls = 0;
       a.tiles_m = cdiv(a.M, 256); a.tiles_n = cdiv(a.K, 256);
-      a.second.tiles_m = cdiv(a.second.M, 256);
-      a.second.tiles0 = a.tiles_m * a.tiles_n;
-      size_t lds2 = 8 * 128 * 128;
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm256_p8_kernel<TO, RM, B1, X3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        attr2 = true;
-      }
-      conv_igemm256_p8_kernel<TO, RM, B1, X3, true><<<(a.tiles_m + a.second.tiles_m) * a.tiles_n, 512, lds2, st>>>(a);
-      UNIT_LAUNCH_CHECK();
-      return UNIT_OK;
+      return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, true>>(pair_grid(a, 256), 512, 8 * 128 * 128, a, st);
     } else {
       unit_set_error("conv_big: pair launches need the 256-row RM schedule with bf16 output");
       return UNIT_ERR_UNSUPPORTED;
@@ -606,30 +596,16 @@ static int launch256_p8(Conv256Args& a, hipStream_t st) {
     const int pers = pe ? atoi(pe) : 1;
     if (pers && a.pm_ncls == 0 && (a.ldy & 7) == 0 && grid > 256 && a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) {
       const size_t lds_p = 7 * 128 * 128 + 8 * EpiCfg<4>::BYTES;          // operand slots up to buffer 1's X1 + the epilogue scratch from there on
-      static bool attr_p = false;
-      if (!attr_p) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm256_p8_kernel<TO, RM, B1, X3, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-        attr_p = true;
-      }
       static int ncu = 0;                    // one workgroup per CU (256 on MI355X); a multiple of 8 so that a workgroup's tiles stay on its XCD's share
       if (ncu == 0) {
         int dev = 0, n = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
         ncu = n / 8 * 8;
       }
-      conv_igemm256_p8_kernel<TO, RM, B1, X3, false, true><<<grid < ncu ? grid : ncu, 512, lds_p, st>>>(a);
-      UNIT_LAUNCH_CHECK();
-      return UNIT_OK;
+      return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, false, true>>(grid < ncu ? grid : ncu, 512, lds_p, a, st);
     }
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm256_p8_kernel<TO, RM, B1, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm256_p8_kernel<TO, RM, B1, X3><<<grid, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3>>(grid, 512, lds, a, st);
 }
 
 int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st) {

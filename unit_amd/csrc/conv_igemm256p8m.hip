@@ -240,7 +240,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8m_kernel(Conv256Args p
           for (int j = 0; j < 4; ++j) v[j] += (n + j < p.K) ? p.bias[n + j] : 0.f;
         }
         if (Rz) {
-          float rr[4]; O4<TO>::load(Rz + off + n, rr);
+          float rr[4]; Out4<TO>::load(Rz + off + n, rr);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] += rr[j];
         }
@@ -249,11 +249,11 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8m_kernel(Conv256Args p
           for (int j = 0; j < 4; ++j) v[j] = fmaxf(v[j], 0.f);
         }
         if (Mk) {
-          float mm[4]; O4<TO>::load(Mk + off + n, mm);
+          float mm[4]; Out4<TO>::load(Mk + off + n, mm);
 #pragma unroll
           for (int j = 0; j < 4; ++j) v[j] = mm[j] > 0.f ? v[j] : 0.f;
         }
-        O4<TO>::store(Y + off + n, v);
+        Out4<TO>::store(Y + off + n, v);
       }
   }
 }
@@ -264,14 +264,7 @@ static int launch256_p8m(Conv256Args& a, hipStream_t st) {
   // operand stages 128 KB; the epilogue reuses them: 8 x 8704 B scratch + 8 x 8 KB pooling areas = 135 168 B
   size_t lds = 8 * EpiCfg<4, 32>::BYTES + 8 * 8192;
   static_assert(8 * EpiCfg<4, 32>::BYTES + 8 * 8192 >= 8 * 128 * 128, "LDS covers the operand stages");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm256_p8m_kernel<TO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  conv_igemm256_p8m_kernel<TO><<<a.tiles_m * a.tiles_n, 512, lds, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm256_p8m_kernel<TO>>(a.tiles_m * a.tiles_n, 512, lds, a, st);
 }
 
 int unit_conv256_p8m_launch(Conv256Args& a, int out_dtype, hipStream_t st) {

@@ -424,14 +424,7 @@ static int launch_lc(ConvDmaArgs& a, hipStream_t st) {
       a.second.tiles0 = total;
       total += a.second.tiles_m * a.tiles_n;
       int grid = total < 256 ? total : 256;
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, true, false, WD>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
-        attr2 = true;
-      }
-      conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, true, false, WD><<<grid, Cf::THREADS, Cf::LDS, st>>>(a);
-      UNIT_LAUNCH_CHECK();
-      return UNIT_OK;
+      return conv_launch<conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, true, false, WD>>(grid, Cf::THREADS, Cf::LDS, a, st);
     } else {
       unit_set_error("conv_lc: pair launches take the tile codes 142 .. 182, 144 .. 164");
       return UNIT_ERR_UNSUPPORTED;
@@ -442,25 +435,10 @@ static int launch_lc(ConvDmaArgs& a, hipStream_t st) {
   if constexpr (X3 && NL == 4 && NSMAX == 3 && !WD) {
     // operand reuse (R3) for the pointwise layers: lo / hi / Wh / Wl of a block staged once each. UNIT_X3_REUSE=0: off (A/B, bit-identity test)
     const char* e = getenv("UNIT_X3_REUSE");
-    if ((e ? atoi(e) : 1) && a.R == 1 && a.S == 1 && a.sk.nseg == 3 && (a.Kgemm / 64) % 3 == 0) {
-      static bool attr3 = false;
-      if (!attr3) {
-        (void)hipFuncSetAttribute((const void*)conv_igemm_lc_kernel<FB, FA, NL, NSMAX, true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
-        attr3 = true;
-      }
-      conv_igemm_lc_kernel<FB, FA, NL, NSMAX, true, false, true><<<grid, Cf::THREADS, Cf::LDS, st>>>(a);
-      UNIT_LAUNCH_CHECK();
-      return UNIT_OK;
-    }
+    if ((e ? atoi(e) : 1) && a.R == 1 && a.S == 1 && a.sk.nseg == 3 && (a.Kgemm / 64) % 3 == 0)
+      return conv_launch<conv_igemm_lc_kernel<FB, FA, NL, NSMAX, true, false, true>>(grid, Cf::THREADS, Cf::LDS, a, st);
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, false, false, WD>, hipFuncAttributeMaxDynamicSharedMemorySize, Cf::LDS);
-    attr_set = true;
-  }
-  conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, false, false, WD><<<grid, Cf::THREADS, Cf::LDS, st>>>(a);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return conv_launch<conv_igemm_lc_kernel<FB, FA, NL, NSMAX, X3, false, false, WD>>(grid, Cf::THREADS, Cf::LDS, a, st);
 }
 
 int unit_conv_lc_launch(ConvDmaArgs& a, int out_dtype, int code, hipStream_t st) {

@@ -448,6 +448,27 @@ def conv_out_size(h, w, r, s, stride, pad):
 _POLICY_CACHE = {}
 
 
+def _conv_geometry(x, r, s, stride, pad, scatter):
+    """(n, h, w, oh, ow, oy_mul, ohf, owf) of a conv over x [N,H,W,C]. scatter = (oy_mul, OHf, OWf): output pixel (n,oh,ow) lands at
+    (n, oh*oy_mul, ow*oy_mul) of an [N,OHf,OWf,.] tensor; None: the plain [N,OH,OW,.] output"""
+    n, h, wd = x.shape[:3]
+    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
+    oy_mul, ohf, owf = (1, oh, ow) if scatter is None else scatter
+    return n, h, wd, oh, ow, oy_mul, ohf, owf
+
+
+def _conv_out(geo, ldy, dtype, device, scattered, x3=False):
+    """a conv's output [N,OHf,OWf,ldy] for a geometry of _conv_geometry: zeroed when the launch scatters into it; x3: an ops.X3"""
+    shape = (geo[0], geo[6], geo[7], ldy)
+    y = zeros(shape, dtype, device) if scattered else torch.empty(shape, dtype=dtype, device=device)
+    return y.as_subclass(X3) if x3 else y
+
+
+def _conv_timed_name(big, dma):
+    """the `_timed` name of a forward conv launch: the 256x256 kernels, the LDS-DMA (4-wave / loader-consumer) kernels, the register-staged one"""
+    return "conv_igemm256" if big else ("conv_igemm_dma" if dma else "conv_igemm")
+
+
 def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=None, relu=False, out_dtype=None,
            out=None, ldy=None, scatter=None, tile_cfg=0):
     """x [N,H,W,C] NHWC ; w [k][r][s][C] (same dtype). Returns y [N,OH,OW,ldy] (or writes the strided scatter target).
@@ -457,19 +478,12 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
         assert out_dtype is None and ldy is None
         return conv2d_x3(x, w, k, r, s, stride, pad, bias=bias, residual=residual, mask_ref=mask_ref, relu=relu, out=out, scatter=scatter,
                          tile=None if tile_cfg == 0 else tile_cfg)
-    n, h, wd, c = x.shape
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
+    c = x.shape[3]
+    geo = n, h, wd, oh, ow, oy_mul, ohf, owf = _conv_geometry(x, r, s, stride, pad, scatter)
     out_dtype = out_dtype or x.dtype
     ldy = ldy or ((k + 3) // 4 * 4)
-    if scatter is None:
-        oy_mul, ohf, owf = 1, oh, ow
-    else:
-        oy_mul, ohf, owf = scatter
     if out is None:
-        if scatter is not None:
-            out = zeros((n, ohf, owf, ldy), out_dtype, x.device)
-        else:
-            out = torch.empty((n, ohf, owf, ldy), dtype=out_dtype, device=x.device)
+        out = _conv_out(geo, ldy, out_dtype, x.device, scatter is not None)
     big, mid, variant = False, -1, 0
     if tile_cfg == 0:          # the two policy functions cost ~5 us per call (the loader / consumer tile search): cached per shape
         pkey = (x.dtype, n * oh * ow, k, c, r * s * c, out_dtype, ldy % 8, BIG_TILE_POLICY, MID_TILE_POLICY)
@@ -485,7 +499,7 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
             big, variant = True, code
         else:
             mid = code
-    with _timed("conv_igemm256" if (big and mid < 0) else ("conv_igemm_dma" if mid >= 0 else "conv_igemm")) as t:
+    with _timed(_conv_timed_name(big and mid < 0, mid >= 0)) as t:
         if mid >= 0:
             check(lib().unit_conv2d_fwd_mid(_p(x), _p(w), _p(out), _p(bias), _p(residual), _p(mask_ref), dt(out_dtype),
                                             n, h, wd, c, k, r, s, stride, pad, oh, ow, ldy, oy_mul, ohf, owf, int(relu), mid, _s()),
@@ -753,19 +767,11 @@ def conv2d_pair(xs, w, k, r, s, stride=1, pad=0, bias=None, residuals=None, mask
     residuals = residuals or (None, None)
     mask_refs = mask_refs or (None, None)
     scatters = scatters or (None, None)
-    geo = []
-    for x, sc in zip(xs, scatters):
-        n, h, wd, _ = x.shape
-        oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-        oy_mul, ohf, owf = (1, oh, ow) if sc is None else sc
-        geo.append((n, h, wd, oh, ow, oy_mul, ohf, owf))
+    geo = [_conv_geometry(x, r, s, stride, pad, sc) for x, sc in zip(xs, scatters)]
     assert geo[0][5] == geo[1][5], "conv2d_pair: one scatter multiplier for both problems"
     ldy = k if x3 else (k + 3) // 4 * 4
     if outs is None:
-        mk = (lambda shape: zeros(shape, x0.dtype, x0.device)) if scatters[0] is not None else (lambda shape: torch.empty(shape, dtype=x0.dtype, device=x0.device))
-        outs = tuple(mk((g[0], g[6], g[7], ldy)) for g in geo)
-        if x3:
-            outs = tuple(o.as_subclass(X3) for o in outs)
+        outs = tuple(_conv_out(g, ldy, x0.dtype, x0.device, scatters[0] is not None, x3) for g in geo)
     ptr = (lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())) if x3 else _p
     if x3:
         for t in tuple(xs) + tuple(outs) + tuple(q for q in residuals + mask_refs if q is not None):
@@ -787,7 +793,7 @@ def conv2d_pair(xs, w, k, r, s, stride=1, pad=0, bias=None, residuals=None, mask
     sec.residual = residuals[1].data_ptr() if residuals[1] is not None else None
     sec.mask_ref = mask_refs[1].data_ptr() if mask_refs[1] is not None else None
     sec.N, sec.H, sec.W, sec.OHf, sec.OWf = g1[0], g1[1], g1[2], g1[6], g1[7]
-    with _timed("conv_igemm256" if kernel == 2 or (kernel in (3, 4) and tile < 0) else ("conv_igemm_dma" if kernel in (1, 3, 4) else "conv_igemm"),
+    with _timed(_conv_timed_name(kernel == 2 or (kernel in (3, 4) and tile < 0), kernel in (1, 3, 4)),
                 ((3 if kernel == 3 else 2) if x3 else 1) * 2.0 * m_tot * k * r * s * c, (sum(x.numel() for x in xs) + m_tot * ldy) * x0.element_size()):
         check(lib().unit_conv2d_fwd_pair(kernel, ptr(xs[0]), _p(w), ptr(outs[0]), _p(bias), ptr(residuals[0]), ptr(mask_refs[0]), mask_c,
                                          BF16 if x3 else dt(x0.dtype), BF16 if x3 else dt(x0.dtype), g0[0], g0[1], g0[2], c, k, r, s, stride, pad, g0[3], g0[4],
@@ -818,16 +824,11 @@ X3_TILE_POLICY = x3_tile_policy
 def conv2d_x3(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=None, relu=False, out=None, scatter=None, tile=None):
     """bf16x3 convolution (unit_conv2d_fwd_x3): x X3 [N,H,W,C], w = weight_prep_x3's forward (or dgrad) copy, residual / mask_ref X3;
     returns an X3 [N,OH,OW,k] (or writes the strided scatter target)."""
-    n, h, wd, c = x.shape
+    c = x.shape[3]
     assert x.is_contiguous() and c % 64 == 0 and k % 8 == 0, "conv2d_x3: C % 64 == 0, K % 8 == 0"
-    oh, ow = conv_out_size(h, wd, r, s, stride, pad)
-    if scatter is None:
-        oy_mul, ohf, owf = 1, oh, ow
-    else:
-        oy_mul, ohf, owf = scatter
+    geo = n, h, wd, oh, ow, oy_mul, ohf, owf = _conv_geometry(x, r, s, stride, pad, scatter)
     if out is None:
-        out = (zeros((n, ohf, owf, k), torch.float32, x.device) if scatter is not None
-               else torch.empty((n, ohf, owf, k), dtype=torch.float32, device=x.device)).as_subclass(X3)
+        out = _conv_out(geo, k, torch.float32, x.device, scatter is not None, x3=True)
     assert type(out) is X3 and out.is_contiguous()
     if residual is not None:
         assert type(residual) is X3 and residual.is_contiguous() and residual.shape[-1] == k
@@ -844,7 +845,7 @@ def conv2d_x3(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref
         if tile is None:
             tile = _POLICY_CACHE[pkey] = X3_TILE_POLICY(m, k, c, segs * r * s * c)
     # flops = the MFMA work issued: three (dgrad with two segments: two) bf16 products per fp32 product
-    with _timed("conv_igemm256" if tile < 0 else "conv_igemm_dma", segs * 2.0 * m * k * r * s * c) as t:
+    with _timed(_conv_timed_name(tile < 0, True), segs * 2.0 * m * k * r * s * c) as t:
         check(lib().unit_conv2d_fwd_x3s(_px(x), _p(w), _px(out), _p(bias), _px(residual), _px(mask_ref), mask_c, n, h, wd, c, k, r, s, stride, pad,
                                         oh, ow, k, oy_mul, ohf, owf, int(relu), int(tile), segs, _s()), "unit_conv2d_fwd_x3s")
         if t.prof is not None:
