@@ -350,6 +350,20 @@ int unit_rpn_loss(const float* head, int ld, int A, int dcol0, const int8_t* lab
 int unit_rpn_loss_w(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx, const float* gt_boxes,
                     int Mcap, const float* anchors, int B, int Ncap, float normalizer, float gscale, float w_cls, float w_loc, float* loss2,
                     void* dhead, int dhead_dtype, float* scratch, size_t scratch_bytes, void* stream);
+/* The box-regression term of unit_rpn_loss_ex / unit_box_reg_loss_ex: Detectron2's `box_reg_loss_type` and `smooth_l1_beta`
+ * (MODEL.RPN.* / MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE, SMOOTH_L1_BETA).
+ *   UNIT_BOXLOSS_SMOOTH_L1: n = |pred - get_deltas(box, gt)| per column; beta < 1e-5: loss n, gradient sign; otherwise 0.5 n^2 / beta
+ *     below beta and n - 0.5 beta from there on (fvcore smooth_l1_loss)
+ *   UNIT_BOXLOSS_GIOU: 1 - I/(U + 1e-7) + (C - U)/(C + 1e-7) of apply_deltas(pred, box) (dw, dh clamped at log(1000/16)) against the
+ *     matched gt box (fvcore giou_loss); the gradient goes back through the decode to the four delta columns
+ * Everything else (rows that count, normalisers, gscale, loss weights, sums, gradient layout and dtype) is as in the plain forms, which
+ * are the _ex forms with (UNIT_BOXLOSS_SMOOTH_L1, 0.0f) and keep their results bit for bit; with any other (loss_type, beta) the row terms are
+ * added in double. An unknown loss_type or a negative beta is UNIT_ERR_ARG. */
+#define UNIT_BOXLOSS_SMOOTH_L1 0
+#define UNIT_BOXLOSS_GIOU 1
+int unit_rpn_loss_ex(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx, const float* gt_boxes,
+                     int Mcap, const float* anchors, int B, int Ncap, float normalizer, float gscale, float w_cls, float w_loc, float* loss2,
+                     void* dhead, int dhead_dtype, float* scratch, size_t scratch_bytes, int loss_type, float beta, void* stream);
 int unit_sup_scores(const float* delta, int ldd, int dcol0, const float* weak, int ldw, int wcol0, int n_oicr, int ncls,
                     const unsigned char* novel_mask_dev, const float* extra, int lde, int ecol0, float* out, int ldo, int R,
                     void* stream);
@@ -361,6 +375,9 @@ int unit_softmax_ce(const float* logits, int ld, int col0, int ncls, const int* 
 int unit_box_reg_loss(const float* bbox, int ld, int col0, int K, const int* labels, const float* rois5, const float* gt_boxes,
                       const float* weights4, int R, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0,
                       unsigned long long* acc, void* stream);
+int unit_box_reg_loss_ex(const float* bbox, int ld, int col0, int K, const int* labels, const float* rois5, const float* gt_boxes,
+                         const float* weights4, int R, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0,
+                         unsigned long long* acc, int loss_type, float beta, void* stream);
 int unit_wsddn_mil(const float* streams, int ld, int ccol0, int dcol0, int K, const int* valid, int S, int B,
                    const unsigned char* multihot, float cls_temp, float det_temp, float mil_multiplier, float gscale, float* loss,
                    float* xr_out, void* dy, int dy_dtype, int ldd, int dyc0, int dyd0, void* stream);

@@ -107,6 +107,8 @@ def get_cfg():
     c.MODEL.ROI_HEADS = CN(NAME="WSROIHeadNoMeta", NUM_CLASSES=20, IN_FEATURES=["res4"], IOU_THRESHOLDS=[0.5], IOU_LABELS=[0, 1],
                            BATCH_SIZE_PER_IMAGE=512, POSITIVE_FRACTION=0.25, SCORE_THRESH_TEST=0.05, NMS_THRESH_TEST=0.5,
                            PROPOSAL_APPEND_GT=True)
+    # BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA: read by the predictors (fast_rcnn.py). BBOX_REG_LOSS_WEIGHT stays unused, as in the reference: its
+    # predictor calls FastRCNNOutputs(...).losses() directly (fast_rcnn.py:438-445) and never applies a loss_weight
     c.MODEL.ROI_BOX_HEAD = CN(NAME="Res5BoxHead", BBOX_REG_WEIGHTS=(10.0, 10.0, 5.0, 5.0), SMOOTH_L1_BETA=0.0,
                               POOLER_RESOLUTION=14, POOLER_SAMPLING_RATIO=0, POOLER_TYPE="ROIAlignV2", CLS_AGNOSTIC_BBOX_REG=False,
                               BBOX_REG_LOSS_TYPE="smooth_l1", BBOX_REG_LOSS_WEIGHT=1.0, TRAIN_ON_PRED_BOXES=False)

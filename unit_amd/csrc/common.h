@@ -91,14 +91,21 @@ __device__ __forceinline__ float wave_reduce_max(float v) {
 // ticket keeps working, the accumulator is handed back zero, and a total >= 2^47 units is reported as NaN -- the loss the single-workgroup form
 // would have produced and TrainerNoMeta.loss_dict()'s anomaly check looks for. (History: 2^-36 units overflowed into the count at 20 000 rows
 // x loss 60; a NaN partial converted to garbage, broke the ticket and left the accumulator dirty for every later launch.)
-__device__ __forceinline__ bool packed_sum_finish(unsigned long long* acc, float partial, int nblk, float* total) {
+// The double form carries partials and total at the accumulator's own resolution (a float total rounds a sum of many rows once more).
+__device__ __forceinline__ bool packed_sum_finish(unsigned long long* acc, double partial, int nblk, double* total) {
   const unsigned long long POISON = 1ull << 47;
-  bool ok = partial >= 0.f && partial < 8388608.f;          // false for NaN
-  unsigned long long q = (ok ? (unsigned long long)((double)partial * 16777216.0) : POISON) + (1ull << 56);
+  bool ok = partial >= 0.0 && partial < 8388608.0;          // false for NaN
+  unsigned long long q = (ok ? (unsigned long long)(partial * 16777216.0) : POISON) + (1ull << 56);
   unsigned long long old = atomicAdd(acc, q);
   if ((int)(old >> 56) != nblk - 1) return false;
   unsigned long long sum = (old + q) & ((1ull << 56) - 1);
-  *total = sum >= POISON ? __builtin_nanf("") : (float)((double)sum * (1.0 / 16777216.0));
+  *total = sum >= POISON ? (double)__builtin_nanf("") : (double)sum * (1.0 / 16777216.0);
   *acc = 0ull;
+  return true;
+}
+__device__ __forceinline__ bool packed_sum_finish(unsigned long long* acc, float partial, int nblk, float* total) {
+  double t;
+  if (!packed_sum_finish(acc, (double)partial, nblk, &t)) return false;
+  *total = (float)t;
   return true;
 }

@@ -16,6 +16,20 @@ __device__ __forceinline__ float block_sum(float v, float* lds /* >= 17 floats *
   return lds[16];
 }
 
+// The same in double: the GIoU / smooth-L1-with-beta terms are tested against a float64 evaluation at the reference's own fp32 error, which
+// leaves a sum of several hundred rows no ulp to lose to its order (the L1 kernels keep the float sums their results were recorded with)
+__device__ __forceinline__ double block_sum_d(double v, double* lds /* >= 17 doubles */) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  __syncthreads();
+  if (lane == 0) lds[wid] = v;
+  __syncthreads();
+  if (threadIdx.x == 0) { double s = 0.0; for (int w = 0; w < nw; ++w) s += lds[w]; lds[16] = s; }
+  __syncthreads();
+  return lds[16];
+}
+
 // packed_sum_finish (common.h): the fixed-point multi-workgroup loss sum
 
 // ---------------------------------------------------------------------------------------------------
@@ -32,16 +46,95 @@ __device__ __forceinline__ f32x4 encode1(f32x4 s, f32x4 t, f32x4 w) {
   return d;
 }
 
-template <typename TD>
+// ---------------------------------------------------------------------------------------------------
+// The per-row term of the two box-regression losses (rpn.py:68-87, fast_rcnn.py:70-87: `box_reg_loss_type`, `smooth_l1_beta`).
+// The C ABI's loss kinds (include/unit_hip.h) ...
+#define UNIT_BOXLOSS_SMOOTH_L1 0
+#define UNIT_BOXLOSS_GIOU 1
+// ... and the kernel bodies they select. (smooth_l1, beta 0) -- Detectron2's default, what the plain exports compute -- keeps the L1 code and
+// the float sums the kernels had before the switch existed: its results stay what they were, bit for bit. Every other beta takes the
+// body that is fvcore's whole smooth_l1_loss (L1 below 1e-5 included) and, like the GIoU body, adds its rows in double.
+#define BOXLOSS_BODY_L1 0
+#define BOXLOSS_BODY_SMOOTH_L1 1
+#define BOXLOSS_BODY_GIOU 2
+static int boxloss_body(int loss_type, float beta) {
+  return loss_type == UNIT_BOXLOSS_GIOU ? BOXLOSS_BODY_GIOU : (beta == 0.f ? BOXLOSS_BODY_L1 : BOXLOSS_BODY_SMOOTH_L1);
+}
+#define UNIT_CHECK_BOXLOSS(what, loss_type, beta)                                                                          \
+  UNIT_CHECK_ARG(loss_type == UNIT_BOXLOSS_SMOOTH_L1 || loss_type == UNIT_BOXLOSS_GIOU, what ": unknown loss_type (0 = smooth_l1, 1 = giou)"); \
+  UNIT_CHECK_ARG(beta >= 0.f, what ": beta must be >= 0")          /* false for NaN too */
+
+__device__ __forceinline__ float sign_of(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
+
+// smooth_l1_loss of one difference df = pred - target, n = |df|: beta < 1e-5: n; otherwise 0.5 n^2 / beta below beta, n - 0.5 beta from
+// there on; *g = d(loss)/d(pred). In double, with the target column from encode_col_d: the fp32 logarithm of the target alone puts a
+// sum of a few hundred |pred - target| an ulp off its float64 value, which is all its test allows.
+__device__ __forceinline__ double smooth_l1_term(double df, float beta, float* g) {
+  double n = fabs(df), b = (double)beta;
+  float sg = df > 0.0 ? 1.f : (df < 0.0 ? -1.f : 0.f);
+  if (beta < 1e-5f) { *g = sg; return n; }
+  if (n < b) { *g = (float)(df / b); return 0.5 * (n * n) / b; }
+  *g = sg;
+  return n - 0.5 * b;
+}
+// column j of encode1 (Box2BoxTransform.get_deltas) in double
+__device__ __forceinline__ double encode_col_d(f32x4 s, f32x4 t, f32x4 w, int j) {
+  double s0 = s[j & 1], s1 = s[2 + (j & 1)], t0 = t[j & 1], t1 = t[2 + (j & 1)];
+  double se = s1 - s0, te = t1 - t0;          // the extents along the column's axis
+  return j < 2 ? (double)w[j] * ((t0 + 0.5 * te) - (s0 + 0.5 * se)) / se : (double)w[j] * log(te / se);
+}
+
+// GIoU (fvcore giou_loss, eps 1e-7) of the box that Box2BoxTransform.apply_deltas(weights w) makes of the deltas d on `box`, against the box g:
+//   1 - I / (U + eps) + (C - U) / (C + eps)       I intersection (0 unless both extents are > 0), U union, C smallest enclosing box
+// and *dd = d(loss)/d(d) through GIoU and through the decode: nothing flows through a dw / dh that the decode clamped at log(1000/16), nor
+// through an empty intersection. Where a min / max has EQUAL operands the gt box's coordinate is taken, i.e. that min / max passes no
+// gradient to the prediction (autograd would give each side half). The value is clamped below at 0 (it is in [0, 2] but for the last bit
+// of I / U at a perfect fit): the fixed-point loss sum takes no negative partial.
+__device__ __forceinline__ float giou_term(f32x4 d, f32x4 box, f32x4 w, f32x4 g, f32x4* dd) {
+  const float SCALE_CLAMP = 4.135166556742356f, EPS = 1e-7f;          // log(1000 / 16)
+  float bw = box[2] - box[0], bh = box[3] - box[1];
+  float cx = box[0] + 0.5f * bw, cy = box[1] + 0.5f * bh;
+  float dw = d[2] / w[2], dh = d[3] / w[3];
+  bool clamp_w = dw > SCALE_CLAMP, clamp_h = dh > SCALE_CLAMP;
+  dw = clamp_w ? SCALE_CLAMP : dw; dh = clamp_h ? SCALE_CLAMP : dh;
+  float pcx = d[0] / w[0] * bw + cx, pcy = d[1] / w[1] * bh + cy;
+  float pw = expf(dw) * bw, ph = expf(dh) * bh;
+  float x1 = pcx - 0.5f * pw, y1 = pcy - 0.5f * ph, x2 = pcx + 0.5f * pw, y2 = pcy + 0.5f * ph;
+  float ix1 = fmaxf(x1, g[0]), iy1 = fmaxf(y1, g[1]), ix2 = fminf(x2, g[2]), iy2 = fminf(y2, g[3]);
+  bool has = iy2 > iy1 && ix2 > ix1;
+  float iw = ix2 - ix1, ih = iy2 - iy1;
+  float inter = has ? iw * ih : 0.f;
+  float w_p = x2 - x1, h_p = y2 - y1;
+  float uni = w_p * h_p + (g[2] - g[0]) * (g[3] - g[1]) - inter;
+  float cw = fmaxf(x2, g[2]) - fminf(x1, g[0]), ch = fmaxf(y2, g[3]) - fminf(y1, g[1]);
+  float area_c = cw * ch;
+  float loss = 1.f - (inter / (uni + EPS) - (area_c - uni) / (area_c + EPS));
+  // d loss / d U (at fixed I, C), / d I (U = A_pred + A_gt - I follows), / d C
+  float g_u = inter / ((uni + EPS) * (uni + EPS)) - 1.f / (area_c + EPS);
+  float g_i = has ? -1.f / (uni + EPS) - g_u : 0.f;
+  float g_c = (uni + EPS) / ((area_c + EPS) * (area_c + EPS));
+  float gx1 = -g_u * h_p - (x1 > g[0] ? g_i * ih : 0.f) - (x1 < g[0] ? g_c * ch : 0.f);
+  float gx2 = g_u * h_p + (x2 < g[2] ? g_i * ih : 0.f) + (x2 > g[2] ? g_c * ch : 0.f);
+  float gy1 = -g_u * w_p - (y1 > g[1] ? g_i * iw : 0.f) - (y1 < g[1] ? g_c * cw : 0.f);
+  float gy2 = g_u * w_p + (y2 < g[3] ? g_i * iw : 0.f) + (y2 > g[3] ? g_c * cw : 0.f);
+  (*dd)[0] = (gx1 + gx2) * bw / w[0];
+  (*dd)[1] = (gy1 + gy2) * bh / w[1];
+  (*dd)[2] = clamp_w ? 0.f : (gx2 - gx1) * (0.5f * pw) / w[2];
+  (*dd)[3] = clamp_h ? 0.f : (gy2 - gy1) * (0.5f * ph) / w[3];
+  return fmaxf(loss, 0.f);
+}
+
+template <typename TD, int BODY>
 __global__ void rpn_loss_kernel(const float* __restrict__ head, int ld, int A, int dcol0, const int8_t* __restrict__ labels,
                                 const int64_t* __restrict__ midx, const float* __restrict__ gt, int Mcap,
-                                const float* __restrict__ anchors, int Ncap, float inv_norm, float gscale, float w_cls, float w_loc,
+                                const float* __restrict__ anchors, int Ncap, float inv_norm, float gscale, float w_cls, float w_loc, float beta,
                                 float* __restrict__ loss2, TD* __restrict__ dhead, float* __restrict__ scratch) {
   __shared__ float lds[17];
   __shared__ int s_last;
   int b = blockIdx.y;
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   float lc = 0.f, ll = 0.f;
+  double lld = 0.0;          // BODY != L1: the anchor's own term, in double like the sums over anchors
   if (i < Ncap) {
     int pix = i / A, a = i - pix * A;
     size_t row = ((size_t)b * (Ncap / A) + pix) * ld;
@@ -58,12 +151,27 @@ __global__ void rpn_loss_kernel(const float* __restrict__ head, int ld, int A, i
       f32x4 an = *reinterpret_cast<const f32x4*>(anchors + 4 * (size_t)i);
       f32x4 g = *reinterpret_cast<const f32x4*>(gt + ((size_t)b * Mcap + midx[(size_t)b * Ncap + i]) * 4);
       const f32x4 w1 = {1.f, 1.f, 1.f, 1.f};
-      f32x4 t = encode1(an, g, w1);
+      const float* p = head + row + dcol0 + 4 * a;
+      if constexpr (BODY == BOXLOSS_BODY_GIOU) {
+        f32x4 d = {p[0], p[1], p[2], p[3]}, gd;
+        lld = (double)giou_term(d, an, w1, g, &gd);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        float df = head[row + dcol0 + 4 * a + j] - t[j];
-        ll += fabsf(df);
-        dd[j] = (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * inv_norm * gscale * w_loc;
+        for (int j = 0; j < 4; ++j) dd[j] = gd[j] * inv_norm * gscale * w_loc;
+      } else if constexpr (BODY == BOXLOSS_BODY_L1) {
+        f32x4 t = encode1(an, g, w1);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float df = p[j] - t[j];
+          ll += fabsf(df);
+          dd[j] = (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * inv_norm * gscale * w_loc;
+        }
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float gd;
+          lld += smooth_l1_term((double)p[j] - encode_col_d(an, g, w1, j), beta, &gd);
+          dd[j] = gd * inv_norm * gscale * w_loc;
+        }
       }
     }
     st(dhead + row + a, dl);
@@ -71,7 +179,14 @@ __global__ void rpn_loss_kernel(const float* __restrict__ head, int ld, int A, i
     for (int j = 0; j < 4; ++j) st(dhead + row + dcol0 + 4 * a + j, dd[j]);
   }
   float sc = block_sum(lc, lds);
-  float sl = block_sum(ll, lds);
+  float sl, sl_lo = 0.f;
+  if constexpr (BODY == BOXLOSS_BODY_L1) sl = block_sum(ll, lds);
+  else {          // the workgroup's sum as a float pair: a third slot per workgroup, behind the ticket
+    __shared__ double ldsd[17];
+    double sd = block_sum_d(lld, ldsd);
+    sl = (float)sd;
+    sl_lo = (float)(sd - (double)sl);
+  }
   // Bit-reproducible sums: every workgroup parks its two partials in its own scratch slot, the last one to arrive adds all slots in
   // a fixed order. Hand-off through device-scope atomics only (a slot is zero and gets exactly one atomicAdd, the reader fetches it
   // with atomicAdd(.., 0)): they execute at the memory side, so no assumption about the per-XCD L2s is needed.
@@ -80,43 +195,53 @@ __global__ void rpn_loss_kernel(const float* __restrict__ head, int ld, int A, i
   if (threadIdx.x == 0) {
     atomicAdd(scratch + 2 * blk, sc);
     atomicAdd(scratch + 2 * blk + 1, sl);
+    if constexpr (BODY != BOXLOSS_BODY_L1) atomicAdd(scratch + 2 * nblk + 1 + blk, sl_lo);
     __threadfence();
     s_last = (atomicAdd(ticket, 1u) == (unsigned)(nblk - 1)) ? 1 : 0;
   }
   __syncthreads();
   if (!s_last) return;
   float tc = 0.f, tl = 0.f;
+  double tld = 0.0;
   for (int j = threadIdx.x; j < nblk; j += blockDim.x) {        // fixed assignment of slots to threads, fixed order per thread
     tc += atomicAdd(scratch + 2 * j, 0.f);
-    tl += atomicAdd(scratch + 2 * j + 1, 0.f);
+    if constexpr (BODY == BOXLOSS_BODY_L1) tl += atomicAdd(scratch + 2 * j + 1, 0.f);
+    else tld += (double)atomicAdd(scratch + 2 * j + 1, 0.f) + (double)atomicAdd(scratch + 2 * nblk + 1 + j, 0.f);
   }
   tc = block_sum(tc, lds);
-  tl = block_sum(tl, lds);
-  if (threadIdx.x == 0) { loss2[0] = tc * inv_norm * w_cls; loss2[1] = tl * inv_norm * w_loc; }
+  if constexpr (BODY == BOXLOSS_BODY_L1) {
+    tl = block_sum(tl, lds);
+    if (threadIdx.x == 0) { loss2[0] = tc * inv_norm * w_cls; loss2[1] = tl * inv_norm * w_loc; }
+  } else {
+    __shared__ double ldsd2[17];
+    tld = block_sum_d(tld, ldsd2);
+    if (threadIdx.x == 0) { loss2[0] = tc * inv_norm * w_cls; loss2[1] = (float)(tld * (double)inv_norm * (double)w_loc); }
+  }
 }
 
-// two partial sums per workgroup + the arrival counter
-extern "C" size_t unit_rpn_loss_scratch_bytes(int B, int Ncap) { return ((size_t)2 * cdiv(Ncap, 256) * (B > 0 ? B : 1) + 1) * sizeof(float); }
-
-extern "C" int unit_rpn_loss_w(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
-                               const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
-                               float gscale, float w_cls, float w_loc, float* loss2, void* dhead, int dhead_dtype, float* scratch,
-                               size_t scratch_bytes, void* stream);
-extern "C" int unit_rpn_loss(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
-                             const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
-                             float gscale, float* loss2, void* dhead, int dhead_dtype, float* scratch, size_t scratch_bytes,
-                             void* stream) {
-  return unit_rpn_loss_w(head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, B, Ncap, normalizer, gscale, 1.0f, 1.0f, loss2, dhead,
-                         dhead_dtype, scratch, scratch_bytes, stream);
-}
+// two partial sums per workgroup + the arrival counter + the low half of the localisation sum (GIoU / smooth-L1 with a beta)
+extern "C" size_t unit_rpn_loss_scratch_bytes(int B, int Ncap) { return ((size_t)3 * cdiv(Ncap, 256) * (B > 0 ? B : 1) + 1) * sizeof(float); }
 
 // w_cls / w_loc: the `loss_weight` dictionary of Detectron2's RPN (rpn.py:100 `losses = {k: v * self.loss_weight.get(k, 1.0)}`;
-// MODEL.RPN.LOSS_WEIGHT and LOSS_WEIGHT * BBOX_REG_LOSS_WEIGHT): both the loss values and their gradients carry them
-extern "C" int unit_rpn_loss_w(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
-                               const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
-                               float gscale, float w_cls, float w_loc, float* loss2, void* dhead, int dhead_dtype, float* scratch,
-                               size_t scratch_bytes, void* stream) {
+// MODEL.RPN.LOSS_WEIGHT and LOSS_WEIGHT * BBOX_REG_LOSS_WEIGHT): both the loss values and their gradients carry them.
+// loss_type / beta: MODEL.RPN.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA (rpn.py:68-87)
+template <typename TD>
+static void rpn_loss_launch(int body, dim3 grid, hipStream_t s, const float* head, int ld, int A, int dcol0, const int8_t* labels,
+                            const int64_t* midx, const float* gt, int Mcap, const float* anchors, int Ncap, float inv, float gscale,
+                            float w_cls, float w_loc, float beta, float* loss2, TD* dhead, float* scratch) {
+  if (body == BOXLOSS_BODY_GIOU)
+    rpn_loss_kernel<TD, BOXLOSS_BODY_GIOU><<<grid, 256, 0, s>>>(head, ld, A, dcol0, labels, midx, gt, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, beta, loss2, dhead, scratch);
+  else if (body == BOXLOSS_BODY_SMOOTH_L1)
+    rpn_loss_kernel<TD, BOXLOSS_BODY_SMOOTH_L1><<<grid, 256, 0, s>>>(head, ld, A, dcol0, labels, midx, gt, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, beta, loss2, dhead, scratch);
+  else
+    rpn_loss_kernel<TD, BOXLOSS_BODY_L1><<<grid, 256, 0, s>>>(head, ld, A, dcol0, labels, midx, gt, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, beta, loss2, dhead, scratch);
+}
+extern "C" int unit_rpn_loss_ex(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
+                                const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
+                                float gscale, float w_cls, float w_loc, float* loss2, void* dhead, int dhead_dtype, float* scratch,
+                                size_t scratch_bytes, int loss_type, float beta, void* stream) {
   UNIT_CHECK_ARG(Ncap % A == 0, "rpn_loss: Ncap % A != 0");
+  UNIT_CHECK_BOXLOSS("rpn_loss", loss_type, beta);
   hipStream_t s = (hipStream_t)stream;
   size_t need = unit_rpn_loss_scratch_bytes(B, Ncap);
   if (scratch == nullptr || scratch_bytes < need) { unit_set_error("rpn_loss: scratch too small"); return UNIT_ERR_WORKSPACE; }
@@ -127,12 +252,27 @@ extern "C" int unit_rpn_loss_w(const float* head, int ld, int A, int dcol0, cons
   if (B == 0 || Ncap == 0) return UNIT_OK;
   dim3 grid(cdiv(Ncap, 256), B);
   float inv = 1.0f / normalizer;
+  int body = boxloss_body(loss_type, beta);
   if (dhead_dtype == UNIT_BF16)
-    rpn_loss_kernel<bf16_t><<<grid, 256, 0, s>>>(head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, loss2, (bf16_t*)dhead, scratch);
+    rpn_loss_launch<bf16_t>(body, grid, s, head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, beta, loss2, (bf16_t*)dhead, scratch);
   else
-    rpn_loss_kernel<float><<<grid, 256, 0, s>>>(head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, loss2, (float*)dhead, scratch);
+    rpn_loss_launch<float>(body, grid, s, head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, Ncap, inv, gscale, w_cls, w_loc, beta, loss2, (float*)dhead, scratch);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
+}
+extern "C" int unit_rpn_loss_w(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
+                               const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
+                               float gscale, float w_cls, float w_loc, float* loss2, void* dhead, int dhead_dtype, float* scratch,
+                               size_t scratch_bytes, void* stream) {
+  return unit_rpn_loss_ex(head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, B, Ncap, normalizer, gscale, w_cls, w_loc, loss2, dhead,
+                          dhead_dtype, scratch, scratch_bytes, UNIT_BOXLOSS_SMOOTH_L1, 0.0f, stream);
+}
+extern "C" int unit_rpn_loss(const float* head, int ld, int A, int dcol0, const int8_t* labels, const int64_t* match_idx,
+                             const float* gt_boxes, int Mcap, const float* anchors, int B, int Ncap, float normalizer,
+                             float gscale, float* loss2, void* dhead, int dhead_dtype, float* scratch, size_t scratch_bytes,
+                             void* stream) {
+  return unit_rpn_loss_w(head, ld, A, dcol0, labels, match_idx, gt_boxes, Mcap, anchors, B, Ncap, normalizer, gscale, 1.0f, 1.0f, loss2, dhead,
+                         dhead_dtype, scratch, scratch_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -358,11 +498,12 @@ extern "C" int unit_softmax_ce(const float* logits, int ld, int col0, int ncls, 
 
 // ---------------------------------------------------------------------------------------------------
 // a11  box regression loss (d2 FastRCNNOutputs.box_reg_loss; arithmetic documented in-tree fast_rcnn.py:37-101):
-//   sum_{fg rows} | bbox[r, 4c:4c+4] - get_deltas(prop, gt; w) |  /  (#rows)       smooth-L1 beta=0 == L1
+//   sum_{fg rows} term(r)  /  (#rows with label >= 0)       term by MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / SMOOTH_L1_BETA (:70-87):
+//   smooth-L1 of bbox[r, 4c:4c+4] - get_deltas(prop, gt; w) (beta < 1e-5: L1), or GIoU of apply_deltas(bbox[r, 4c:4c+4], prop; w) against gt
 // ---------------------------------------------------------------------------------------------------
-template <typename TD>
+template <typename TD, int BODY>
 __global__ void box_reg_loss_kernel(const float* __restrict__ bbox, int ld, int col0, int K, const int* __restrict__ labels,
-                                    const float* __restrict__ rois5, const float* __restrict__ gtb, f32x4 w, int R, float gscale,
+                                    const float* __restrict__ rois5, const float* __restrict__ gtb, f32x4 w, int R, float gscale, float beta,
                                     float* __restrict__ loss, TD* __restrict__ dy, int ldd, int dcol0, unsigned long long* __restrict__ pacc) {
   __shared__ float lds[17];
   float cnt = 0.f;
@@ -370,38 +511,83 @@ __global__ void box_reg_loss_kernel(const float* __restrict__ bbox, int ld, int 
   float total = block_sum(cnt, lds);
   float inv = total > 0.f ? 1.f / total : 0.f;
   float acc = 0.f;
+  double accd = 0.0;          // BODY != L1
   for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < R; r += gridDim.x * blockDim.x) {
     int lab = labels[r];
     if (dy) for (int c = 0; c < 4 * K; ++c) st(dy + (size_t)r * ldd + dcol0 + c, 0.f);
     if (lab < 0 || lab >= K) continue;
     f32x4 pb = {rois5[(size_t)r * 5 + 1], rois5[(size_t)r * 5 + 2], rois5[(size_t)r * 5 + 3], rois5[(size_t)r * 5 + 4]};
     f32x4 g = *reinterpret_cast<const f32x4*>(gtb + (size_t)r * 4);
-    f32x4 t = encode1(pb, g, w);
+    if constexpr (BODY == BOXLOSS_BODY_GIOU) {
+      const float* p = bbox + (size_t)r * ld + col0 + 4 * lab;
+      f32x4 d = {p[0], p[1], p[2], p[3]}, gd;
+      accd += (double)giou_term(d, pb, w, g, &gd);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float df = bbox[(size_t)r * ld + col0 + 4 * lab + j] - t[j];
-      acc += fabsf(df);
-      if (dy) st(dy + (size_t)r * ldd + dcol0 + 4 * lab + j, (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * inv * gscale);
+      for (int j = 0; j < 4; ++j)
+        if (dy) st(dy + (size_t)r * ldd + dcol0 + 4 * lab + j, gd[j] * inv * gscale);
+    } else if constexpr (BODY == BOXLOSS_BODY_L1) {
+      f32x4 t = encode1(pb, g, w);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float df = bbox[(size_t)r * ld + col0 + 4 * lab + j] - t[j];
+        acc += fabsf(df);
+        if (dy) st(dy + (size_t)r * ldd + dcol0 + 4 * lab + j, (df > 0.f ? 1.f : (df < 0.f ? -1.f : 0.f)) * inv * gscale);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        float gd;
+        accd += smooth_l1_term((double)bbox[(size_t)r * ld + col0 + 4 * lab + j] - encode_col_d(pb, g, w, j), beta, &gd);
+        if (dy) st(dy + (size_t)r * ldd + dcol0 + 4 * lab + j, gd * inv * gscale);
+      }
     }
   }
-  float s = block_sum(acc, lds);
-  if (threadIdx.x == 0) {
-    if (gridDim.x == 1) *loss = s * inv;
-    else { float t; if (packed_sum_finish(pacc, s, gridDim.x, &t)) *loss = t * inv; }
+  if constexpr (BODY == BOXLOSS_BODY_L1) {
+    float s = block_sum(acc, lds);
+    if (threadIdx.x == 0) {
+      if (gridDim.x == 1) *loss = s * inv;
+      else { float t; if (packed_sum_finish(pacc, s, gridDim.x, &t)) *loss = t * inv; }
+    }
+  } else {
+    __shared__ double ldsd[17];
+    double s = block_sum_d(accd, ldsd);
+    if (threadIdx.x == 0) {
+      double t = s;
+      if (gridDim.x == 1 || packed_sum_finish(pacc, s, gridDim.x, &t)) *loss = total > 0.f ? (float)(t / (double)total) : 0.f;
+    }
   }
+}
+template <typename TD>
+static void box_reg_loss_launch(int body, int g, int th, hipStream_t s, const float* bbox, int ld, int col0, int K, const int* labels,
+                                const float* rois5, const float* gt_boxes, f32x4 w, int R, float gscale, float beta, float* loss, TD* dy,
+                                int ldd, int dcol0, unsigned long long* acc) {
+  if (body == BOXLOSS_BODY_GIOU)
+    box_reg_loss_kernel<TD, BOXLOSS_BODY_GIOU><<<g, th, 0, s>>>(bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, beta, loss, dy, ldd, dcol0, acc);
+  else if (body == BOXLOSS_BODY_SMOOTH_L1)
+    box_reg_loss_kernel<TD, BOXLOSS_BODY_SMOOTH_L1><<<g, th, 0, s>>>(bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, beta, loss, dy, ldd, dcol0, acc);
+  else
+    box_reg_loss_kernel<TD, BOXLOSS_BODY_L1><<<g, th, 0, s>>>(bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, beta, loss, dy, ldd, dcol0, acc);
+}
+extern "C" int unit_box_reg_loss_ex(const float* bbox, int ld, int col0, int K, const int* labels, const float* rois5, const float* gt_boxes,
+                                    const float* weights4, int R, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0,
+                                    unsigned long long* acc, int loss_type, float beta, void* stream) {
+  UNIT_CHECK_BOXLOSS("box_reg_loss", loss_type, beta);
+  hipStream_t s = (hipStream_t)stream;
+  f32x4 w = {weights4[0], weights4[1], weights4[2], weights4[3]};
+  int th, g = loss_grid(R, acc, &th);
+  int body = boxloss_body(loss_type, beta);
+  if (dy_dtype == UNIT_BF16)
+    box_reg_loss_launch<bf16_t>(body, g, th, s, bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, beta, loss, (bf16_t*)dy, ldd, dcol0, acc);
+  else
+    box_reg_loss_launch<float>(body, g, th, s, bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, beta, loss, (float*)dy, ldd, dcol0, acc);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
 }
 extern "C" int unit_box_reg_loss(const float* bbox, int ld, int col0, int K, const int* labels, const float* rois5, const float* gt_boxes,
                                  const float* weights4, int R, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0,
                                  unsigned long long* acc, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  f32x4 w = {weights4[0], weights4[1], weights4[2], weights4[3]};
-  int th, g = loss_grid(R, acc, &th);
-  if (dy_dtype == UNIT_BF16)
-    box_reg_loss_kernel<bf16_t><<<g, th, 0, s>>>(bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, loss, (bf16_t*)dy, ldd, dcol0, acc);
-  else
-    box_reg_loss_kernel<float><<<g, th, 0, s>>>(bbox, ld, col0, K, labels, rois5, gt_boxes, w, R, gscale, loss, (float*)dy, ldd, dcol0, acc);
-  UNIT_LAUNCH_CHECK();
-  return UNIT_OK;
+  return unit_box_reg_loss_ex(bbox, ld, col0, K, labels, rois5, gt_boxes, weights4, R, gscale, loss, dy, dy_dtype, ldd, dcol0, acc,
+                              UNIT_BOXLOSS_SMOOTH_L1, 0.0f, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

@@ -208,7 +208,16 @@ class SupervisedDetectorOutputsBase(nn.Module):
         super().__init__()
         self.num_classes = k = cfg.MODEL.ROI_HEADS.NUM_CLASSES
         self.box_dim = 4
-        assert not cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG and cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA == 0.0
+        bh = cfg.MODEL.ROI_BOX_HEAD
+        assert not bh.CLS_AGNOSTIC_BBOX_REG, ("CLS_AGNOSTIC_BBOX_REG: the reference's own similarity transfer reshapes the box deltas to "
+                                              "[R, K, 4] (fast_rcnn.py:414), so it cannot run class-agnostic either")
+        # fast_rcnn.py:70-87 through :438-445: the box term, "smooth_l1" (with SMOOTH_L1_BETA) or "giou" -- a switch of the loss kernel
+        # (unit_box_reg_loss_ex)
+        self.box_reg_loss_type, self.smooth_l1_beta = str(bh.BBOX_REG_LOSS_TYPE), float(bh.SMOOTH_L1_BETA)
+        if self.box_reg_loss_type not in ops.BOX_LOSS_TYPES:
+            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")
+        if not self.smooth_l1_beta >= 0.0:
+            raise ValueError(f"MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA must be >= 0, got {self.smooth_l1_beta}")
         self.bbox_reg_weights = tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
         self.test_score_thresh = cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST
         self.test_nms_thresh = cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
@@ -260,7 +269,7 @@ class SupervisedDetectorOutputsBase(nn.Module):
         dy = ops.zeros((lin_sup.shape[0], self.group.kp), grad_dtype, lin_sup.device)
         ops.softmax_ce(scores, 0, k + 1, roi_cls, dy=dy, dcol0=self.col_cls, loss_out=loss_out[0:1])
         ops.box_reg_loss(lin_sup, self.col_bbox, k, roi_cls, rois5, roi_gt, self.bbox_reg_weights, dy=dy, dcol0=self.col_bbox,
-                         loss_out=loss_out[1:2])
+                         loss_out=loss_out[1:2], loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)
         return dy, scores
 
 
@@ -357,7 +366,8 @@ class SupervisedDetectorOutputsBase(nn.Module):
             else:
                 with torch.no_grad():
                     out["loss_cls"] = ops.softmax_ce(scores.float().contiguous(), 0, k + 1, gc)[0]
-                    out["loss_box_reg"] = ops.box_reg_loss(bbox.float().contiguous(), 0, k, gc, rois5, gb, self.bbox_reg_weights)[0]
+                    out["loss_box_reg"] = ops.box_reg_loss(bbox.float().contiguous(), 0, k, gc, rois5, gb, self.bbox_reg_weights,
+                                                           loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)[0]
         if weak_predictions is not None:
             out.update(self.weak_detector_head.losses(weak_predictions, weak_proposals, weak_targets))
         return out
@@ -406,5 +416,6 @@ class SupervisedDetectorOutputsFineTune(SupervisedDetectorOutputsBase):
         k = self.num_classes
         dy = ops.zeros((scores.shape[0], self.group_ft.kp), grad_dtype, scores.device)
         ops.softmax_ce(scores, 0, k + 1, roi_cls, dy=dy, dcol0=self.col_cls, loss_out=loss_out[0:1])
-        ops.box_reg_loss(bbox, 0, k, roi_cls, rois5, roi_gt, self.bbox_reg_weights, dy=dy, dcol0=self.col_bbox, loss_out=loss_out[1:2])
+        ops.box_reg_loss(bbox, 0, k, roi_cls, rois5, roi_gt, self.bbox_reg_weights, dy=dy, dcol0=self.col_bbox, loss_out=loss_out[1:2],
+                         loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)
         return dy

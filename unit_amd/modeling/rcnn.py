@@ -490,7 +490,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 ops.metrics_rpn(c.anchor_labels, c.metrics[step_metrics.RPN:step_metrics.RPN + 5])
             _, c.dhead = ops.rpn_loss(head[:n_sup], rpn.num_anchors, rpn.num_anchors, c.anchor_labels, c.anchor_match, batch.gt_boxes,
                                       anchors, rpn.batch_size_per_image * n_sup, dt, loss_out=c.rpn_losses,
-                                      weights=(rpn.loss_weight["loss_rpn_cls"], rpn.loss_weight["loss_rpn_loc"]))
+                                      weights=(rpn.loss_weight["loss_rpn_cls"], rpn.loss_weight["loss_rpn_loc"]),
+                                      loss_type=rpn.box_reg_loss_type, beta=rpn.smooth_l1_beta)
 
         if side_rpn:
             self._reattach_grads()

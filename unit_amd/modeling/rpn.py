@@ -119,7 +119,13 @@ class WSRPN(nn.Module):
         # rpn.py:100 -- the loss kernel scales values and gradients (unit_rpn_loss_w). All shipped yaml leave both at 1.0.
         self.loss_weight = {"loss_rpn_cls": float(r.LOSS_WEIGHT), "loss_rpn_loc": float(r.BBOX_REG_LOSS_WEIGHT) * float(r.LOSS_WEIGHT)}
         self.min_box_size = float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE)
-        assert r.BBOX_REG_LOSS_TYPE == "smooth_l1" and r.SMOOTH_L1_BETA == 0.0 and tuple(r.BBOX_REG_WEIGHTS) == (1.0, 1.0, 1.0, 1.0)
+        # rpn.py:68-87: the localisation term, "smooth_l1" (with SMOOTH_L1_BETA) or "giou" -- a switch of the loss kernel (unit_rpn_loss_ex)
+        self.box_reg_loss_type, self.smooth_l1_beta = str(r.BBOX_REG_LOSS_TYPE), float(r.SMOOTH_L1_BETA)
+        if self.box_reg_loss_type not in ops.BOX_LOSS_TYPES:
+            raise ValueError(f"Invalid rpn box reg loss type '{self.box_reg_loss_type}'")
+        if not self.smooth_l1_beta >= 0.0:
+            raise ValueError(f"MODEL.RPN.SMOOTH_L1_BETA must be >= 0, got {self.smooth_l1_beta}")
+        assert tuple(r.BBOX_REG_WEIGHTS) == (1.0, 1.0, 1.0, 1.0), "RPN BBOX_REG_WEIGHTS (1, 1, 1, 1): rpn_decode_select has them built in"
 
     # ---- a4: RPN.label_and_sample_anchors -- IoU + Matcher[0.3,0.7;lowq] + explicit-permutation sampling
     def label_and_sample_anchors(self, anchors, gt_boxes, gt_count, perm):
@@ -131,7 +137,8 @@ class WSRPN(nn.Module):
     def losses(self, head, labels, match_idx, gt_boxes, anchors, grad_dtype):
         a = self.num_anchors
         n = head.shape[0]
-        return ops.rpn_loss(head, a, a, labels, match_idx, gt_boxes, anchors, self.batch_size_per_image * n, grad_dtype)
+        return ops.rpn_loss(head, a, a, labels, match_idx, gt_boxes, anchors, self.batch_size_per_image * n, grad_dtype,
+                            loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)
 
     # ---- a6: predict_proposals / find_top_rpn_proposals, sync-free (counts stay on the device)
     def predict_proposals(self, head, anchors, image_hw_dev, training, out=None):

@@ -138,7 +138,8 @@ class _RpnFn(torch.autograd.Function):
             labels, match, _ = module.label_and_sample_anchors(anchors, gt_boxes, gt_count, perm)
             _, ctx.dhead = ops.rpn_loss(head, module.num_anchors, module.num_anchors, labels, match, gt_boxes, anchors,
                                         module.batch_size_per_image * n, dtype, loss_out=losses,
-                                        weights=(module.loss_weight["loss_rpn_cls"], module.loss_weight["loss_rpn_loc"]))
+                                        weights=(module.loss_weight["loss_rpn_cls"], module.loss_weight["loss_rpn_loc"]),
+                                        loss_type=module.box_reg_loss_type, beta=module.smooth_l1_beta)
             io["anchor_labels"] = labels
         if io["sizes"] is not None:
             hw = torch.tensor(io["sizes"], dtype=torch.float32).to(dev)
@@ -470,7 +471,8 @@ class _SupLossFn(torch.autograd.Function):
         dbb = ops.zeros(bb.shape, torch.float32, bb.device)
         loss = ops.zeros(2, torch.float32, sc.device)
         ops.softmax_ce(sc, 0, k + 1, meta["gc"], dy=dsc, dcol0=0, loss_out=loss[0:1])
-        ops.box_reg_loss(bb, 0, k, meta["gc"], meta["rois5"], meta["gb"], bp.bbox_reg_weights, dy=dbb, dcol0=0, loss_out=loss[1:2])
+        ops.box_reg_loss(bb, 0, k, meta["gc"], meta["rois5"], meta["gb"], bp.bbox_reg_weights, dy=dbb, dcol0=0, loss_out=loss[1:2],
+                         loss_type=bp.box_reg_loss_type, beta=bp.smooth_l1_beta)
         ctx.saved = (dsc, dbb)
         return loss
 

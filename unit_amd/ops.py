@@ -1305,17 +1305,38 @@ def roi_align_bwd_gather(gout, n_images, h, w, rois, out, pooled_size=14, bin_st
 
 
 # ------------------------------------------------------------------------------------------------ losses
-def rpn_loss(head, a, dcol0, labels, match_idx, gt_boxes, anchors, normalizer, grad_dtype, gscale=1.0, loss_out=None, weights=(1.0, 1.0)):
-    """weights = (loss_rpn_cls, loss_rpn_loc) factors of Detectron2's RPN `loss_weight` (rpn.py:100)"""
+BOX_LOSS_TYPES = {"smooth_l1": 0, "giou": 1}          # include/unit_hip.h: UNIT_BOXLOSS_SMOOTH_L1 / UNIT_BOXLOSS_GIOU
+
+
+def _box_loss_args(loss_type, beta, what):
+    """(kind, beta) of the _ex loss exports, or None for Detectron2's default (smooth-L1 with beta 0 == L1): that one keeps its own export, so
+    a default model's launch list is what it always was"""
+    if loss_type not in BOX_LOSS_TYPES:
+        raise ValueError(f"Invalid {what} loss type '{loss_type}'")
+    beta = float(beta)
+    if not beta >= 0.0:
+        raise ValueError(f"smooth_l1_beta must be >= 0, got {beta}")
+    return None if (loss_type == "smooth_l1" and beta == 0.0) else (BOX_LOSS_TYPES[loss_type], beta)
+
+
+def rpn_loss(head, a, dcol0, labels, match_idx, gt_boxes, anchors, normalizer, grad_dtype, gscale=1.0, loss_out=None, weights=(1.0, 1.0),
+             loss_type="smooth_l1", beta=0.0):
+    """weights = (loss_rpn_cls, loss_rpn_loc) factors of Detectron2's RPN `loss_weight` (rpn.py:100); loss_type / beta = its `box_reg_loss_type`
+    ("smooth_l1" | "giou") and `smooth_l1_beta` (rpn.py:68-87)"""
+    ex = _box_loss_args(loss_type, beta, "rpn box reg")
     b, hw, ld = head.shape
     ncap = anchors.shape[0]
     loss2 = loss_out if loss_out is not None else torch.empty(2, dtype=torch.float32, device=head.device)
     dhead = torch.empty((b, hw, ld), dtype=grad_dtype, device=head.device)
     nbytes = lib().unit_rpn_loss_scratch_bytes(b, ncap)
     scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=head.device)
-    check(lib().unit_rpn_loss_w(_p(head), ld, a, dcol0, _p(labels), _p(match_idx), _p(gt_boxes), gt_boxes.shape[1], _p(anchors), b, ncap,
-                                float(normalizer), float(gscale), float(weights[0]), float(weights[1]), _p(loss2), _p(dhead), dt(grad_dtype),
-                                _p(scratch), nbytes, _s()), "rpn_loss")
+    args = (_p(head), ld, a, dcol0, _p(labels), _p(match_idx), _p(gt_boxes), gt_boxes.shape[1], _p(anchors), b, ncap, float(normalizer),
+            float(gscale), float(weights[0]), float(weights[1]), _p(loss2), _p(dhead), dt(grad_dtype), _p(scratch), nbytes)
+    with _timed("rpn_loss"):
+        if ex is None:
+            check(lib().unit_rpn_loss_w(*args, _s()), "rpn_loss")
+        else:
+            check(lib().unit_rpn_loss_ex(*args, ex[0], ex[1], _s()), "rpn_loss_ex")
     return loss2, dhead
 
 
@@ -1360,13 +1381,19 @@ def softmax_ce(logits, col0, ncls, labels, weights=None, dy=None, dcol0=0, gscal
     return loss
 
 
-def box_reg_loss(bbox, col0, k, labels, rois5, gt_boxes, weights, dy=None, dcol0=0, gscale=1.0, loss_out=None):
+def box_reg_loss(bbox, col0, k, labels, rois5, gt_boxes, weights, dy=None, dcol0=0, gscale=1.0, loss_out=None, loss_type="smooth_l1", beta=0.0):
+    """loss_type / beta: FastRCNNOutputs' `box_reg_loss_type` ("smooth_l1" | "giou") and `smooth_l1_beta` (fast_rcnn.py:70-87)"""
+    ex = _box_loss_args(loss_type, beta, "bbox reg")
     r, ld = bbox.shape
     loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=bbox.device)
     w = (ctypes.c_float * 4)(*weights)
-    check(lib().unit_box_reg_loss(_p(bbox), ld, col0, k, _p(labels), _p(rois5), _p(gt_boxes), w, r, float(gscale), _p(loss), _p(dy),
-                                  dt(dy.dtype) if dy is not None else 0, dy.shape[1] if dy is not None else 0, dcol0, _p(_loss_acc(bbox.device)),
-                                  _s()), "box_reg_loss")
+    args = (_p(bbox), ld, col0, k, _p(labels), _p(rois5), _p(gt_boxes), w, r, float(gscale), _p(loss), _p(dy),
+            dt(dy.dtype) if dy is not None else 0, dy.shape[1] if dy is not None else 0, dcol0, _p(_loss_acc(bbox.device)))
+    with _timed("box_reg_loss"):
+        if ex is None:
+            check(lib().unit_box_reg_loss(*args, _s()), "box_reg_loss")
+        else:
+            check(lib().unit_box_reg_loss_ex(*args, ex[0], ex[1], _s()), "box_reg_loss_ex")
     return loss
 
 
