@@ -383,6 +383,19 @@ int unit_wsddn_mil(const float* streams, int ld, int ccol0, int dcol0, int K, co
                    float* xr_out, void* dy, int dy_dtype, int ldd, int dyc0, int dyd0, void* stream);
 int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
                       const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, void* stream);
+/* unit_oicr_targets plus the box of the pseudo-GT that each row's Matcher picked -- the `gt_boxes` field of the proposals that
+ * compute_loss_inputs(return_proposals=True) returns (weak_detector_fast_rcnn.py:399-401 through label_and_sample_proposals :337-346), which
+ * FastRCNNOutputsRegression's box loss regresses to (:253). gt_boxes [B*S][4], 16-byte aligned, may be NULL: zeros for rows with
+ * valid < 0 and for images without pseudo-GT (:343-346). labels / weights are those of unit_oicr_targets bit for bit; the plain entry is this
+ * one with gt_boxes = NULL. */
+int unit_oicr_targets_ex(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
+                         const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, float* gt_boxes,
+                         void* stream);
+/* oicr_mean_scores (weak_detector_fast_rcnn.py:248): out[r, 0..K] = (sum_t softmax(logits[r, col0 + t*step : +K+1])) / n over the n
+ * refinement streams, added in stream order, each softmax as unit_softmax_rows computes it; rows with valid[r] < 0 (valid may be NULL) are
+ * written as zeros. The two targets kernels read the result in mode 0 (first K columns, ld = ldo). */
+int unit_softmax_mean(const float* logits, int ld, int col0, int step, int n, int K, const int* valid, float* out, int ldo, int R,
+                      void* stream);
 int unit_sum_losses(const float* losses, int n, float* out, void* stream);
 /* PCL loss (weak detector TYPE "PCL"; the model calls it after unit_pcl_targets): PCLFunction
  * modeling/roi_heads/pcl_loss.py:6-61 as applied per image at weak_detector_fast_rcnn.py:233-238 -> *loss = sum_b loss_b / B and, with dy,
@@ -412,6 +425,16 @@ int unit_pcl_targets(const float* src, int ld, int col0, int mode, int step, con
                      float bg_thresh, float graph_iou_thresh, int max_pc_num, int* labels, float* cls_weights, int* gt_assign, int* n_pc,
                      int* pc_labels, int* pc_count, float* pc_img_cls_weights, float* pc_probs, int ldc, void* workspace,
                      size_t workspace_bytes, void* stream);
+/* unit_pcl_targets plus the box of the cluster centre that each row's Matcher picked (compute_pcl_loss_inputs with return_proposals=True,
+ * weak_detector_fast_rcnn.py:509-518 through label_and_sample_proposals :337-346): gt_boxes [n_streams][B*S][4], 16-byte aligned, may be
+ * NULL; zeros for rows with valid < 0 and for images without a centre. Every other output is unit_pcl_targets' bit for bit; the plain entry
+ * is this one with gt_boxes = NULL. The regression branch calls it with the mean score (unit_softmax_mean, mode 0) as src and the
+ * regression_branch_cls logits as nxt (:252). */
+int unit_pcl_targets_ex(const float* src, int ld, int col0, int mode, int step, const float* nxt, int ldn, int ncol0, int nmode, int nstep,
+                        int K, const float* rois5, const int* valid, int S, int B, int n_streams, const unsigned char* multihot,
+                        float fg_thresh, float bg_thresh, float graph_iou_thresh, int max_pc_num, int* labels, float* cls_weights,
+                        int* gt_assign, int* n_pc, int* pc_labels, int* pc_count, float* pc_img_cls_weights, float* pc_probs, int ldc,
+                        float* gt_boxes, void* workspace, size_t workspace_bytes, void* stream);
 /* sampling permutations (d2 `subsample_labels` -> torch.randperm; call sites rpn.py:41, roi_heads.py:563): keys [B][n] = hash of
  * (seed, *counter_dev, stream_id, b, i) as positive finite floats; `unit_sort_desc_stable` of them yields the permutation.
  * The device-resident counter is advanced by unit_counter_bump (graph-replay safe). */

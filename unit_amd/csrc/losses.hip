@@ -853,7 +853,8 @@ __device__ __forceinline__ float iou_box(const f32x4 a, const f32x4 b) {
 
 __global__ void oicr_targets_kernel(const float* __restrict__ src, int ld, int col0, int mode, int K, const float* __restrict__ rois5,
                                     const int* __restrict__ valid, int S, const unsigned char* __restrict__ multihot,
-                                    float fg_thresh, float bg_thresh, int* __restrict__ labels, float* __restrict__ weights) {
+                                    float fg_thresh, float bg_thresh, int* __restrict__ labels, float* __restrict__ weights,
+                                    float* __restrict__ gt_boxes /* [B*S][4] or null */) {
   __shared__ float s_val[16]; __shared__ int s_idx[16];
   __shared__ f32x4 gbox[MIL_MAXK]; __shared__ float gscore[MIL_MAXK]; __shared__ int gcls[MIL_MAXK];
   __shared__ int s_zero_row, s_ngt;
@@ -901,9 +902,11 @@ __global__ void oicr_targets_kernel(const float* __restrict__ src, int ld, int c
     __syncthreads();
   }
   if (tid >= S) return;
-  if (!have) { labels[row] = -1; weights[row] = 0.f; return; }
+  // the row's matched pseudo-GT box (label_and_sample_proposals :337-346): zeros for an empty slot and for an image without pseudo-GT
+  f32x4* gout = gt_boxes ? reinterpret_cast<f32x4*>(gt_boxes) + row : nullptr;
+  if (!have) { labels[row] = -1; weights[row] = 0.f; if (gout) *gout = f32x4{0.f, 0.f, 0.f, 0.f}; return; }
   int ng = s_ngt;
-  if (ng == 0) { labels[row] = K; weights[row] = 0.f; return; }
+  if (ng == 0) { labels[row] = K; weights[row] = 0.f; if (gout) *gout = f32x4{0.f, 0.f, 0.f, 0.f}; return; }
   f32x4 me = {rois5[row * 5 + 1], rois5[row * 5 + 2], rois5[row * 5 + 3], rois5[row * 5 + 4]};
   float best = -1.f; int bi = 0;
   for (int g = 0; g < ng; ++g) { float v = iou_box(gbox[g], me); if (v > best) { best = v; bi = g; } }
@@ -911,14 +914,60 @@ __global__ void oicr_targets_kernel(const float* __restrict__ src, int ld, int c
   float w = gscore[bi];
   if (best < bg_thresh) w = 0.f;                      // :392-396
   labels[row] = lab; weights[row] = w;
+  if (gout) *gout = gbox[bi];                         // the box of the pseudo-GT the Matcher picked, whatever its label (:338-341)
+}
+extern "C" int unit_oicr_targets_ex(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S,
+                                    int B, const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights,
+                                    float* gt_boxes, void* stream) {
+  UNIT_CHECK_ARG(K < MIL_MAXK && S <= 1024, "oicr_targets: K >= 96 or S > 1024");
+  UNIT_CHECK_ARG(((uintptr_t)gt_boxes & 15) == 0, "oicr_targets: gt_boxes must be 16-byte aligned");
+  if (B == 0) return UNIT_OK;
+  int threads = ((S + 63) / 64) * 64;
+  oicr_targets_kernel<<<B, threads, 0, (hipStream_t)stream>>>(src, ld, col0, mode, K, rois5, valid, S, multihot, fg_thresh, bg_thresh, labels,
+                                                              weights, gt_boxes);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
 }
 extern "C" int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S,
                                  int B, const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights,
                                  void* stream) {
-  UNIT_CHECK_ARG(K < MIL_MAXK && S <= 1024, "oicr_targets: K >= 96 or S > 1024");
-  if (B == 0) return UNIT_OK;
-  int threads = ((S + 63) / 64) * 64;
-  oicr_targets_kernel<<<B, threads, 0, (hipStream_t)stream>>>(src, ld, col0, mode, K, rois5, valid, S, multihot, fg_thresh, bg_thresh, labels, weights);
+  return unit_oicr_targets_ex(src, ld, col0, mode, K, rois5, valid, S, B, multihot, fg_thresh, bg_thresh, labels, weights, nullptr, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// a12  regression branch: oicr_mean_scores  weak_detector_fast_rcnn.py:248
+//   out[r, 0..K] = (sum_t softmax(logits[r, col0 + t*step : +K+1])) / n, streams added in order (torch.mean over the stack); the per-row
+//   softmax is unit_softmax_rows' arithmetic. Rows with valid[r] < 0 (empty slots) are written as zeros. One thread per row: R*n*(K+1)
+//   floats in, R*(K+1) out -- nothing to tile.
+// ---------------------------------------------------------------------------------------------------
+__global__ void softmax_mean_kernel(const float* __restrict__ logits, int ld, int col0, int step, int n, int K, const int* __restrict__ valid,
+                                    float* __restrict__ out, int ldo, int R) {
+  int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  float* y = out + (size_t)r * ldo;
+  if (valid && valid[r] < 0) {
+    for (int c = 0; c <= K; ++c) y[c] = 0.f;
+    return;
+  }
+  for (int t = 0; t < n; ++t) {
+    const float* p = logits + (size_t)r * ld + col0 + (size_t)t * step;
+    float mx = -INFINITY;
+    for (int c = 0; c <= K; ++c) mx = fmaxf(mx, p[c]);
+    float se = 0.f;
+    for (int c = 0; c <= K; ++c) se += expf(p[c] - mx);
+    for (int c = 0; c <= K; ++c) {
+      float v = expf(p[c] - mx) / se;
+      y[c] = t == 0 ? v : y[c] + v;
+    }
+  }
+  for (int c = 0; c <= K; ++c) y[c] = y[c] / (float)n;
+}
+extern "C" int unit_softmax_mean(const float* logits, int ld, int col0, int step, int n, int K, const int* valid, float* out, int ldo, int R,
+                                 void* stream) {
+  UNIT_CHECK_ARG(n >= 1 && K >= 1 && step >= 0 && col0 >= 0 && R >= 0, "softmax_mean: bad shape");
+  UNIT_CHECK_ARG(ld >= col0 + (n - 1) * step + K + 1 && ldo >= K + 1, "softmax_mean: columns outside the row stride");
+  if (R == 0) return UNIT_OK;
+  softmax_mean_kernel<<<cdiv(R, 128), 128, 0, (hipStream_t)stream>>>(logits, ld, col0, step, n, K, valid, out, ldo, R);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

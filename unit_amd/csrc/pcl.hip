@@ -472,6 +472,7 @@ __global__ __launch_bounds__(PT_NT) void pcl_targets_kernel(const float* __restr
                                                            float* __restrict__ cls_w, int* __restrict__ gt_assign, int* __restrict__ n_pc,
                                                            int* __restrict__ pc_labels, int* __restrict__ pc_count,
                                                            float* __restrict__ pc_icw, float* __restrict__ pc_probs, int ldc,
+                                                           float* __restrict__ gt_boxes /* [n_streams][B*S][4] or null */,
                                                            float* __restrict__ ws, int S4) {
   __shared__ PtShared s;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x, t = blockIdx.y;
@@ -483,6 +484,8 @@ __global__ __launch_bounds__(PT_NT) void pcl_targets_kernel(const float* __restr
   float* mx0 = gscore + S4; float* se0 = mx0 + S4; float* mx1 = se0 + S4; float* se1 = mx1 + S4;
   const PtSrc q0 = {src, ld, col0 + t * step, mode, mx0, se0}, q1 = {nxt, ldn, ncol0 + t * nstep, nmode, mx1, se1};
   labels += unit * S; cls_w += unit * S; gt_assign += unit * S;
+  // the row's matched centre box (label_and_sample_proposals :337-346), written by the thread that owns the row
+  f32x4* gout = gt_boxes ? reinterpret_cast<f32x4*>(gt_boxes) + unit * S : nullptr;
   pc_labels += unit * ldc; pc_count += unit * ldc; pc_icw += unit * ldc; pc_probs += unit * ldc;
 
   // ---- the image's rows; softmax statistics of the logits inputs
@@ -614,8 +617,11 @@ __global__ __launch_bounds__(PT_NT) void pcl_targets_kernel(const float* __restr
   const int M = s.npc, poison = s.poison;
   for (int i = tid; i < S; i += PT_NT) {
     const size_t row = row0 + i;
-    if (valid[row] < 0) { labels[i] = -1; cls_w[i] = 0.f; gt_assign[i] = -1; continue; }
-    if (M == 0) { labels[i] = K; cls_w[i] = poison ? NAN : 0.f; gt_assign[i] = -1; continue; }
+    if (valid[row] < 0 || M == 0) {
+      if (gout) gout[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (valid[row] < 0) { labels[i] = -1; cls_w[i] = 0.f; gt_assign[i] = -1; continue; }
+      labels[i] = K; cls_w[i] = poison ? NAN : 0.f; gt_assign[i] = -1; continue;
+    }
     const float* r = rois5 + row * 5;
     const f32x4 me = {r[1], r[2], r[3], r[4]};
     float best = -1.f;
@@ -626,6 +632,7 @@ __global__ __launch_bounds__(PT_NT) void pcl_targets_kernel(const float* __restr
     if (best < bg_thresh) w = 0.f;
     cls_w[i] = poison ? NAN : w;
     gt_assign[i] = best < fg_thresh ? -1 : bi;
+    if (gout) gout[i] = gbox[bi];
   }
   __threadfence_block();
   __syncthreads();
@@ -660,12 +667,13 @@ extern "C" size_t unit_workspace_bytes_pcl_targets(int B, int S, int n_streams) 
   return sizeof(float) * 13 * s4 * (size_t)B * (size_t)n_streams + 16;
 }
 
-extern "C" int unit_pcl_targets(const float* src, int ld, int col0, int mode, int step, const float* nxt, int ldn, int ncol0, int nmode,
-                                int nstep, int K, const float* rois5, const int* valid, int S, int B, int n_streams,
-                                const unsigned char* multihot, float fg_thresh, float bg_thresh, float graph_iou_thresh, int max_pc_num,
-                                int* labels, float* cls_weights, int* gt_assign, int* n_pc, int* pc_labels, int* pc_count,
-                                float* pc_img_cls_weights, float* pc_probs, int ldc, void* workspace, size_t workspace_bytes,
-                                void* stream) {
+extern "C" int unit_pcl_targets_ex(const float* src, int ld, int col0, int mode, int step, const float* nxt, int ldn, int ncol0, int nmode,
+                                   int nstep, int K, const float* rois5, const int* valid, int S, int B, int n_streams,
+                                   const unsigned char* multihot, float fg_thresh, float bg_thresh, float graph_iou_thresh, int max_pc_num,
+                                   int* labels, float* cls_weights, int* gt_assign, int* n_pc, int* pc_labels, int* pc_count,
+                                   float* pc_img_cls_weights, float* pc_probs, int ldc, float* gt_boxes, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  UNIT_CHECK_ARG(((uintptr_t)gt_boxes & 15) == 0, "pcl_targets: gt_boxes must be 16-byte aligned");
   UNIT_CHECK_ARG(K > 0 && K < 96 && S >= 0 && B >= 0 && n_streams >= 0, "pcl_targets: bad shape (K >= 96?)");
   UNIT_CHECK_ARG(S <= PT_SMAX, "pcl_targets: S > 2048 rows per image");
   UNIT_CHECK_ARG((mode == 0 || mode == 1) && (nmode == 0 || nmode == 1), "pcl_targets: mode is 0 (probabilities) or 1 (logits)");
@@ -680,7 +688,17 @@ extern "C" int unit_pcl_targets(const float* src, int ld, int col0, int mode, in
   float* ws = reinterpret_cast<float*>(((uintptr_t)workspace + 15) & ~(uintptr_t)15);
   pcl_targets_kernel<<<dim3(B, n_streams), PT_NT, 0, (hipStream_t)stream>>>(
       src, ld, col0, mode, step, nxt, ldn, ncol0, nmode, nstep, K, rois5, valid, S, B, multihot, fg_thresh, bg_thresh, graph_iou_thresh,
-      max_pc_num, labels, cls_weights, gt_assign, n_pc, pc_labels, pc_count, pc_img_cls_weights, pc_probs, ldc, ws, (S + 3) & ~3);
+      max_pc_num, labels, cls_weights, gt_assign, n_pc, pc_labels, pc_count, pc_img_cls_weights, pc_probs, ldc, gt_boxes, ws, (S + 3) & ~3);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
+}
+extern "C" int unit_pcl_targets(const float* src, int ld, int col0, int mode, int step, const float* nxt, int ldn, int ncol0, int nmode,
+                                int nstep, int K, const float* rois5, const int* valid, int S, int B, int n_streams,
+                                const unsigned char* multihot, float fg_thresh, float bg_thresh, float graph_iou_thresh, int max_pc_num,
+                                int* labels, float* cls_weights, int* gt_assign, int* n_pc, int* pc_labels, int* pc_count,
+                                float* pc_img_cls_weights, float* pc_probs, int ldc, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+  return unit_pcl_targets_ex(src, ld, col0, mode, step, nxt, ldn, ncol0, nmode, nstep, K, rois5, valid, S, B, n_streams, multihot, fg_thresh,
+                             bg_thresh, graph_iou_thresh, max_pc_num, labels, cls_weights, gt_assign, n_pc, pc_labels, pc_count,
+                             pc_img_cls_weights, pc_probs, ldc, nullptr, workspace, workspace_bytes, stream);
 }

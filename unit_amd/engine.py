@@ -446,7 +446,7 @@ class TrainerNoMeta:
         dropped (csrc/sort_nms.hip, csrc/boxes.hip), ReLU epilogues squash NaN (fmaxf)."""
         import math
         vals = self.last_losses.cpu().tolist()
-        d = dict(zip(LOSS_NAMES, vals))
+        d = dict(zip(getattr(self.model, "loss_names", LOSS_NAMES), vals))
         if detect_anomaly and not all(math.isfinite(v) for v in vals):
             raise FloatingPointError(f"Loss became infinite or NaN at iteration={self.iter}!\nloss_dict = {d}")
         return d

@@ -1,9 +1,10 @@
 """Box predictors -- MI355X counterparts of
   * SupervisedDetectorOutputsBase      /root/reference/modeling/roi_heads/fast_rcnn.py:293-468
   * SupervisedDetectorOutputsFineTune  /root/reference/modeling/roi_heads/fast_rcnn.py:471-533
-  * WeakDetectorOutputsBase            /root/reference/modeling/roi_heads/weak_detector_fast_rcnn.py:39-519 (TYPE "OICR" and "PCL")
+  * WeakDetectorOutputsBase            /root/reference/modeling/roi_heads/weak_detector_fast_rcnn.py:39-519 (TYPE "OICR" and "PCL",
+                                       with or without REGRESSION_BRANCH)
 Parameter names equal the reference's (`cls_score_delta`, `bbox_pred_delta`, `cls_score_ft`, `bbox_pred_ft`,
-`weak_detector_head.{classifier_stream,detection_stream,oicr_predictors.k}`, `embeddings.weight`).
+`weak_detector_head.{classifier_stream,detection_stream,oicr_predictors.k,regression_branch_cls,regression_branch_bbox}`, `embeddings.weight`).
 All Linear layers that share an input run as one fused GEMM (LinearGroup); the loss kernels emit loss + gradient."""
 import os
 
@@ -13,6 +14,44 @@ from torch import nn
 from .. import ops
 from ..layers import Linear, LinearGroup
 from ..structures import FAST_RCNN_REGISTRY, WEAK_DETECTOR_FAST_RCNN_REGISTRY
+
+
+REGRESSION_LOSSES = ["loss_regression_cls", "loss_regression_bbox"]          # FastRCNNOutputsRegression.losses weak_detector_fast_rcnn.py:35-36
+
+
+def _box_loss_cfg(cfg):
+    """(BBOX_REG_LOSS_TYPE, SMOOTH_L1_BETA) of fast_rcnn.py:70-87, checked"""
+    bh = cfg.MODEL.ROI_BOX_HEAD
+    loss_type, beta = str(bh.BBOX_REG_LOSS_TYPE), float(bh.SMOOTH_L1_BETA)
+    if loss_type not in ops.BOX_LOSS_TYPES:
+        raise ValueError(f"Invalid bbox reg loss type '{loss_type}'")
+    if not beta >= 0.0:
+        raise ValueError(f"MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA must be >= 0, got {beta}")
+    return loss_type, beta
+
+
+def _detect(head, probs, bbox, proposals):
+    """d2 fast_rcnn_inference (drop bg, apply_deltas, clip, score > thresh, per-class NMS, top-k) on the device, for ragged
+    probabilities [R, K + 1] / deltas [R, 4K] -> (list[Instances(pred_boxes, scores, pred_classes)], list[filter_inds])"""
+    from .inference import pack_proposal_instances
+    from ..structures import Boxes, Instances
+    dev, k = probs.device, head.num_classes
+    props, pcount = pack_proposal_instances(proposals, dev)
+    n, rcap = props.shape[0], props.shape[1]
+    pp = torch.zeros((n * rcap, k + 1), dtype=torch.float32, device=dev)
+    bb = torch.zeros((n * rcap, 4 * k), dtype=torch.float32, device=dev)
+    o = 0
+    for i, p in enumerate(proposals):      # ragged -> fixed slots (API boundary; the fused eval path never leaves fixed slots)
+        pp[i * rcap:i * rcap + len(p)], bb[i * rcap:i * rcap + len(p)] = probs[o:o + len(p)], bbox[o:o + len(p)].float()
+        o += len(p)
+    hw = torch.tensor([p.image_size for p in proposals], dtype=torch.float32).to(dev)
+    boxes, sc, cls, roi, cnt = ops.detections(pp, bb, props, pcount, hw, head.bbox_reg_weights, head.test_score_thresh,
+                                              head.test_nms_thresh, head.test_topk_per_image)
+    res, inds = [], []
+    for i, c in enumerate(cnt.tolist()):
+        res.append(Instances(proposals[i].image_size, pred_boxes=Boxes(boxes[i, :c]), scores=sc[i, :c], pred_classes=cls[i, :c].long()))
+        inds.append(roi[i, :c].long())
+    return res, inds
 
 
 def _freeze_by_first_component(module, layers):
@@ -26,8 +65,13 @@ class WeakDetectorOutputsBase(nn.Module):
     def __init__(self, cfg, input_shape):
         super().__init__()
         wd = cfg.MODEL.ROI_HEADS.FAST_RCNN.WEAK_DETECTOR
-        assert wd.TYPE in ("OICR", "PCL") and not wd.REGRESSION_BRANCH and not wd.OICR_REGRESSION_BRANCH, \
-            "WEAK_DETECTOR.TYPE is \"OICR\" or \"PCL\", without the regression branches (REGRESSION_BRANCH / OICR_REGRESSION_BRANCH)"
+        assert wd.TYPE in ("OICR", "PCL"), "WEAK_DETECTOR.TYPE is \"OICR\" or \"PCL\""
+        assert not wd.OICR_REGRESSION_BRANCH, \
+            ("WEAK_DETECTOR.OICR_REGRESSION_BRANCH (a box regressor per refinement stream) is not supported: the reference's own non-TTA inference "
+             "hands the list of per-stream deltas to apply_deltas (weak_detector_fast_rcnn.py:176-179, 270-277). REGRESSION_BRANCH is supported")
+        self.regression_branch = bool(wd.REGRESSION_BRANCH)
+        assert not self.regression_branch or wd.OICR_ITER > 0, \
+            "WEAK_DETECTOR.REGRESSION_BRANCH needs OICR_ITER > 0: its pseudo-GT comes from the mean of the refinement streams (:248)"
         assert wd.TYPE != "PCL" or wd.NUM_KMEANS_CLUSTER == 3, \
             "TYPE \"PCL\" needs NUM_KMEANS_CLUSTER == 3: the only k-means the device kernel restates (csrc/pcl.hip, tests/golden/pcl_kmeans.py)"
         self.weak_detector_type = wd.TYPE
@@ -46,17 +90,45 @@ class WeakDetectorOutputsBase(nn.Module):
         self.oicr_predictors = nn.ModuleList([Linear(self.input_size, k + 1) for _ in range(self.oicr_iter)])
         for l in self.oicr_predictors:
             nn.init.normal_(l.weight, std=0.01)
+        members = [self.classifier_stream, self.detection_stream] + list(self.oicr_predictors)
+        if self.regression_branch:          # :93-99 -- two more column blocks of the head's one fused GEMM / weight-gradient launch
+            self.regression_branch_cls = Linear(self.input_size, k + 1)
+            self.regression_branch_bbox = Linear(self.input_size, 4 * k)
+            nn.init.normal_(self.regression_branch_bbox.weight, std=0.001)
+            nn.init.normal_(self.regression_branch_cls.weight, std=0.01)
+            members += [self.regression_branch_cls, self.regression_branch_bbox]
+            self.box_reg_loss_type, self.smooth_l1_beta = _box_loss_cfg(cfg)
+        self.bbox_reg_weights = tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
+        self.test_score_thresh = cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST
+        self.test_nms_thresh = cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
+        self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         _freeze_by_first_component(self, cfg.MODEL.FREEZE_LAYERS.FAST_RCNN)
-        self.group = LinearGroup([self.classifier_stream, self.detection_stream] + list(self.oicr_predictors))
+        self.group = LinearGroup(members)
         self.col_cls, self.col_det = self.group.cols[0], self.group.cols[1]
-        self.col_oicr = self.group.cols[2:]
+        self.col_oicr = self.group.cols[2:2 + self.oicr_iter]
+        if self.regression_branch:
+            self.col_reg_cls, self.col_reg_bbox = self.group.cols[2 + self.oicr_iter:]
+            assert all(b - a == k + 1 for a, b in zip(self.col_oicr, self.col_oicr[1:]))          # unit_softmax_mean: equally spaced streams
+
+    @property
+    def n_losses(self):
+        """loss_im_cls, loss_oicr_1..n (+ loss_regression_cls, loss_regression_bbox)"""
+        return 1 + self.oicr_iter + (2 if self.regression_branch else 0)
+
+    # ---- what the supervised predictor adds to its own outputs (fast_rcnn.py:360-374): the columns of this head's fused Linear that carry
+    # the weak scores -- the refinement streams, whose mean is taken, or regression_branch_cls alone (:363-364)
+    @property
+    def score_cols(self):
+        return (self.col_reg_cls, 1) if self.regression_branch else (self.col_oicr[0], self.oicr_iter)
 
     def prepare(self, dtype, version):
         self.group.prepare(dtype, version)
 
     # ---- a12: WeakDetectorOutputsBase.losses weak_detector_fast_rcnn.py:189-255 (fused fwd + gradient into `dy`)
-    def fused_losses(self, lin, rois5, valid, rois_per_image, n_images, multihot, loss_out, grad_dtype, side_stream=None):
+    def fused_losses(self, lin, rois5, valid, rois_per_image, n_images, multihot, loss_out, grad_dtype, side_stream=None, reg_loss_out=None):
         """lin fp32 [Rw, kp] = fused Linear outputs on the weak RoIs. Returns dy [Rw, kp] (grad_dtype).
+        REGRESSION_BRANCH (:245-254): reg_loss_out [2] receives loss_regression_cls / loss_regression_bbox; the branch's four launches
+        (mean score, pseudo-GT with boxes, weighted cross-entropy, box loss) read forward outputs only, so they go where iterations >= 1 go.
         Only OICR iteration 0 needs the MIL output x_r; iterations >= 1 take their pseudo-GT from softmax(oicr_{k-1} logits),
         which are forward outputs: with `side_stream` they run beside the (single-workgroup-per-image, latency-bound) MIL
         kernel instead of behind it. Every launch writes its own columns of dy / its own loss slot."""
@@ -70,6 +142,25 @@ class WeakDetectorOutputsBase(nn.Module):
                 lab, wts = ops.oicr_targets(lin, self.col_oicr[it - 1], 1, k, rois5, valid, rois_per_image, n_images, multihot,
                                             self.fg_threshold, self.bg_threshold)
             ops.softmax_ce(lin, self.col_oicr[it], k + 1, lab, weights=wts, dy=dy, dcol0=self.col_oicr[it], loss_out=loss_out[1 + it:2 + it])
+
+        def regression():
+            """:245-254: pseudo-GT from the mean of the refinement streams' softmaxes, FastRCNNOutputsRegression on the branch's two outputs"""
+            step = self.col_oicr[1] - self.col_oicr[0] if self.oicr_iter > 1 else 0
+            mean = ops.softmax_mean(lin, self.col_oicr[0], step, self.oicr_iter, k, valid)
+            if self.weak_detector_type == "PCL":          # :252 -- the "next iteration" is regression_branch_cls; its pc_* tables are not consumed
+                t = ops.pcl_targets(mean, 0, 0, lin, self.col_reg_cls, 1, k, rois5, valid, rois_per_image, n_images, multihot,
+                                    ldc=self.max_pc_num * k, fg_thresh=self.fg_threshold, bg_thresh=self.bg_threshold,
+                                    graph_iou_thresh=self.graph_iou_threshold, max_pc_num=self.max_pc_num, want_boxes=True)
+                lab, wts, gtb = t["labels"][0], t["cls_weights"][0], t["gt_boxes"][0]
+            else:
+                lab, wts, gtb = ops.oicr_targets(mean, 0, 0, k, rois5, valid, rois_per_image, n_images, multihot, self.fg_threshold,
+                                                 self.bg_threshold, want_boxes=True)
+            ops.softmax_ce(lin, self.col_reg_cls, k + 1, lab, weights=wts, dy=dy, dcol0=self.col_reg_cls, loss_out=reg_loss_out[0:1])
+            ops.box_reg_loss(lin, self.col_reg_bbox, k, lab, rois5, gtb, self.bbox_reg_weights, dy=dy, dcol0=self.col_reg_bbox,
+                             loss_out=reg_loss_out[1:2], loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)
+
+        reg = self.regression_branch
+        assert not reg or reg_loss_out is not None, "REGRESSION_BRANCH: fused_losses needs reg_loss_out [2]"
 
         def pcl(its, xr):
             """TYPE "PCL" (:225-238): unit_pcl_targets for the consecutive iterations `its` in one launch, then unit_pcl_loss per stream.
@@ -94,34 +185,45 @@ class WeakDetectorOutputsBase(nn.Module):
 
         if self.weak_detector_type == "PCL":
             later = list(range(1, self.oicr_iter))
-            if side_stream is not None and later:
+            if side_stream is not None and (later or reg):
                 side_stream.wait_stream(torch.cuda.current_stream())
                 with torch.cuda.stream(side_stream):
-                    pcl(later, None)
+                    if later:
+                        pcl(later, None)
+                    if reg:
+                        regression()
             _, xr = ops.wsddn_mil(lin, self.col_cls, self.col_det, k, valid, rois_per_image, n_images, multihot, self.classifier_temp,
                                   self.detector_temp, self.mil_multiplier, dy=dy, dyc0=self.col_cls, dyd0=self.col_det, loss_out=loss_out[0:1])
             if self.oicr_iter > 0:
                 pcl([0], xr)
-            if side_stream is not None and later:
+            if side_stream is not None and (later or reg):
                 torch.cuda.current_stream().wait_stream(side_stream)
-            elif later:
-                pcl(later, None)
+            else:
+                if later:
+                    pcl(later, None)
+                if reg:
+                    regression()
             return dy
 
-        if side_stream is not None and self.oicr_iter > 1:
+        on_side = side_stream is not None and (self.oicr_iter > 1 or reg)
+        if on_side:
             main = torch.cuda.current_stream()
             side_stream.wait_stream(main)                    # dy zeroed, lin complete
             with torch.cuda.stream(side_stream):
                 for it in range(1, self.oicr_iter):
                     oicr(it, None)
+                if reg:
+                    regression()
         _, xr = ops.wsddn_mil(lin, self.col_cls, self.col_det, k, valid, rois_per_image, n_images, multihot, self.classifier_temp,
                               self.detector_temp, self.mil_multiplier, dy=dy, dyc0=self.col_cls, dyd0=self.col_det, loss_out=loss_out[0:1])
         oicr(0, xr)
-        if side_stream is not None and self.oicr_iter > 1:
+        if on_side:
             torch.cuda.current_stream().wait_stream(side_stream)
         else:
             for it in range(1, self.oicr_iter):
                 oicr(it, None)
+            if reg:
+                regression()
         return dy
 
 
@@ -133,8 +235,9 @@ class WeakDetectorOutputsBase(nn.Module):
         return self.group.fwd(ops.cast(x_weak.contiguous(), dtype))
 
     def forward(self, x_weak):
-        """:148-165 -> ([classifier_stream / T_cls, detection_stream / T_det, [oicr_k], [], None, None], None) in training (the outputs
-        carry an autograd graph: one node over the fused Linear, modeling/train_modules.py), `evaluation(x_weak)` otherwise"""
+        """:148-165 -> ([classifier_stream / T_cls, detection_stream / T_det, [oicr_k], [], regression_cls, regression_bbox], None) in training
+        (the last two None without REGRESSION_BRANCH; the outputs carry an autograd graph: one node over the fused Linear,
+        modeling/train_modules.py), `evaluation(x_weak)` otherwise"""
         if not self.training:
             return self.evaluation(x_weak)
         from .train_modules import _WeakPredictFn, _anchor
@@ -143,26 +246,32 @@ class WeakDetectorOutputsBase(nn.Module):
         lin = _WeakPredictFn.apply(x, self)
         cs = lin[:, self.col_cls:self.col_cls + k] / self.classifier_temp
         ds = lin[:, self.col_det:self.col_det + k] / self.detector_temp
-        return [cs, ds, [lin[:, c:c + k + 1] for c in self.col_oicr], [], None, None], None
+        rc = lin[:, self.col_reg_cls:self.col_reg_cls + k + 1] if self.regression_branch else None
+        rb = lin[:, self.col_reg_bbox:self.col_reg_bbox + 4 * k] if self.regression_branch else None
+        return [cs, ds, [lin[:, c:c + k + 1] for c in self.col_oicr], [], rc, rb], None
 
     @torch.no_grad()
     def evaluation(self, x_weak):
-        """:167-187 (OICR_ITER > 0, no regression branches) -> ([[oicr_k logits], zeros(R, 4K)], None)"""
+        """:167-187 -> ([regression_cls, regression_bbox], None) under REGRESSION_BRANCH (:169-171); otherwise (OICR_ITER > 0)
+        ([[oicr_k logits], zeros(R, 4K)], None)"""
         lin, k = self._lin(x_weak), self.num_classes
+        if self.regression_branch:
+            return [lin[:, self.col_reg_cls:self.col_reg_cls + k + 1], lin[:, self.col_reg_bbox:self.col_reg_bbox + 4 * k]], None
         return [[lin[:, c:c + k + 1] for c in self.col_oicr], torch.zeros((lin.shape[0], 4 * k), device=lin.device)], None
 
     def losses(self, weak_predictions, weak_proposals, weak_targets):
-        """:189-255 -> {'loss_im_cls', 'loss_oicr_1..n'} (HIP kernels unit_wsddn_mil / unit_oicr_targets / unit_softmax_ce; TYPE "PCL":
+        """:189-255 -> {'loss_im_cls', 'loss_oicr_1..n'} (+ {'loss_regression_cls', 'loss_regression_bbox'} under REGRESSION_BRANCH) (HIP kernels unit_wsddn_mil / unit_oicr_targets / unit_softmax_ce; TYPE "PCL":
         unit_pcl_targets / unit_pcl_loss, whose refinement gradient ignores the weight that arrives, as PCLFunction.backward does). With predictions
         that carry a graph (training-mode forward) the losses do too: one autograd node whose backward hands out the gradient the loss kernels
         emit, scaled by the weight that arrives. weak_predictions = forward()'s list, weak_proposals = list[Instances(proposal_boxes)],
         weak_targets = list[LongTensor]."""
         cs, ds, oicr = weak_predictions[0], weak_predictions[1], weak_predictions[2]
-        with_graph = torch.is_grad_enabled() and any(t.requires_grad for t in [cs, ds] + list(oicr))
+        reg = [weak_predictions[4], weak_predictions[5]] if self.regression_branch else []
+        with_graph = torch.is_grad_enabled() and any(t.requires_grad for t in [cs, ds] + list(oicr) + reg)
         with torch.set_grad_enabled(with_graph):
-            return self._losses(cs, ds, oicr, weak_proposals, weak_targets, with_graph)
+            return self._losses(cs, ds, oicr, weak_proposals, weak_targets, with_graph, reg)
 
-    def _losses(self, cs, ds, oicr, weak_proposals, weak_targets, with_graph):
+    def _losses(self, cs, ds, oicr, weak_proposals, weak_targets, with_graph, reg=()):
         k, dev = self.num_classes, cs.device
         sizes = [len(p) for p in weak_proposals]
         b, s = len(sizes), max(sizes)
@@ -178,6 +287,9 @@ class WeakDetectorOutputsBase(nn.Module):
             lin[rows, self.col_det:self.col_det + k] = ds[o:o + n].float() * self.detector_temp
             for c, lg in zip(self.col_oicr, oicr):
                 lin[rows, c:c + k + 1] = lg[o:o + n].float()
+            if self.regression_branch:
+                lin[rows, self.col_reg_cls:self.col_reg_cls + k + 1] = reg[0][o:o + n].float()
+                lin[rows, self.col_reg_bbox:self.col_reg_bbox + 4 * k] = reg[1][o:o + n].float()
             rois5[rows, 0] = i
             rois5[rows, 1:] = (pr.proposal_boxes.tensor if hasattr(pr.proposal_boxes, "tensor") else pr.proposal_boxes).to(dev)
             valid[rows] = 0
@@ -187,17 +299,40 @@ class WeakDetectorOutputsBase(nn.Module):
             from .train_modules import _WeakLossFn
             loss = _WeakLossFn.apply(lin, self, dict(rois5=rois5, valid=valid, s=s, b=b, multihot=multihot))
         else:
-            loss = torch.zeros(1 + self.oicr_iter, dtype=torch.float32, device=dev)
-            self.fused_losses(lin, rois5, valid, s, b, multihot, loss, torch.float32)
+            loss = torch.zeros(self.n_losses, dtype=torch.float32, device=dev)
+            reg_kw = dict(reg_loss_out=loss[1 + self.oicr_iter:]) if self.regression_branch else {}
+            self.fused_losses(lin, rois5, valid, s, b, multihot, loss, torch.float32, **reg_kw)
         out = {"loss_im_cls": loss[0]}
         out.update({f"loss_oicr_{i + 1}": loss[1 + i] for i in range(self.oicr_iter)})
+        if self.regression_branch:
+            out.update({n: loss[1 + self.oicr_iter + i] for i, n in enumerate(REGRESSION_LOSSES)})
         return out
 
     def predict_probs(self, predictions, proposals):
-        """:280-287: sum_k softmax(oicr_k) split per image"""
+        """:280-287: sum_k softmax(oicr_k), or softmax(regression_cls) under REGRESSION_BRANCH (:284-285), split per image"""
         scores, _ = predictions
-        p = sum(ops.softmax_rows(sc.contiguous().float(), self.num_classes + 1) for sc in scores)
+        if self.regression_branch:
+            p = ops.softmax_rows(scores.contiguous().float(), self.num_classes + 1)
+        else:
+            p = sum(ops.softmax_rows(sc.contiguous().float(), self.num_classes + 1) for sc in scores)
         return p.split([len(q) for q in proposals], dim=0)
+
+    @torch.no_grad()
+    def predict_boxes(self, predictions, proposals):
+        """:270-278: Box2BoxTransform.apply_deltas of the [R, 4K] deltas on the proposals, split per image (unit_box_decode)"""
+        _, deltas = predictions
+        tb = lambda v: (v.tensor if hasattr(v, "tensor") else v)
+        boxes = torch.cat([tb(p.proposal_boxes) for p in proposals]).to(deltas.device).float().contiguous()
+        out = ops.box_decode(deltas.float().contiguous(), boxes, self.bbox_reg_weights, self.num_classes)
+        return out.split([len(p) for p in proposals], dim=0)
+
+    @torch.no_grad()
+    def inference(self, predictions, proposals, tta=False):
+        """:289-306 -> (list[Instances(pred_boxes, scores, pred_classes)], list[filter_inds]) through the detection kernels"""
+        if tta:
+            raise NotImplementedError("TTA is outside the hot path (SURVEY.md section 2)")
+        probs = torch.cat(self.predict_probs(predictions, proposals), 0)
+        return _detect(self, probs, predictions[1], proposals)
 
 
 @FAST_RCNN_REGISTRY.register()
@@ -213,11 +348,7 @@ class SupervisedDetectorOutputsBase(nn.Module):
                                               "[R, K, 4] (fast_rcnn.py:414), so it cannot run class-agnostic either")
         # fast_rcnn.py:70-87 through :438-445: the box term, "smooth_l1" (with SMOOTH_L1_BETA) or "giou" -- a switch of the loss kernel
         # (unit_box_reg_loss_ex)
-        self.box_reg_loss_type, self.smooth_l1_beta = str(bh.BBOX_REG_LOSS_TYPE), float(bh.SMOOTH_L1_BETA)
-        if self.box_reg_loss_type not in ops.BOX_LOSS_TYPES:
-            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")
-        if not self.smooth_l1_beta >= 0.0:
-            raise ValueError(f"MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA must be >= 0, got {self.smooth_l1_beta}")
+        self.box_reg_loss_type, self.smooth_l1_beta = _box_loss_cfg(cfg)
         self.bbox_reg_weights = tuple(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_WEIGHTS)
         self.test_score_thresh = cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST
         self.test_nms_thresh = cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
@@ -226,8 +357,15 @@ class SupervisedDetectorOutputsBase(nn.Module):
         self.weak_detector_head = WEAK_DETECTOR_FAST_RCNN_REGISTRY.get(cfg.MODEL.ROI_HEADS.FAST_RCNN.WEAK_DETECTOR.NAME)(cfg, input_shape)
         self.cls_score_delta = Linear(self.input_size, k + 1)
         self.bbox_pred_delta = Linear(self.input_size, k * 4)
+        self.regression_branch = self.weak_detector_head.regression_branch
+        assert not (self.finetune and self.regression_branch), \
+            ("SupervisedDetectorOutputsFineTune with WEAK_DETECTOR.REGRESSION_BRANCH is not supported: the fine-tune stage on top of the weak "
+             "regression branch is not built (DESIGN.md section 8); SupervisedDetectorOutputsBase is")
         nn.init.constant_(self.cls_score_delta.weight, 0.)       # fast_rcnn.py:319
-        nn.init.normal_(self.bbox_pred_delta.weight, std=0.001)  # :321
+        if self.regression_branch:
+            nn.init.constant_(self.bbox_pred_delta.weight, 0.)   # :322-323: the weak branch's deltas are the starting point
+        else:
+            nn.init.normal_(self.bbox_pred_delta.weight, std=0.001)  # :321
         emb = None
         path = cfg.MODEL.ROI_HEADS.EMBEDDING_PATH
         if path and os.path.exists(path):
@@ -265,12 +403,23 @@ class SupervisedDetectorOutputsBase(nn.Module):
         Returns dy [R, kp] in grad_dtype."""
         k = self.num_classes
         wh = self.weak_detector_head
-        scores = ops.sup_scores(lin_sup, self.col_cls, lin_sup_weak, wh.col_oicr[0], wh.oicr_iter, k + 1, self._novel_mask)
+        wcol, wn = wh.score_cols
+        scores = ops.sup_scores(lin_sup, self.col_cls, lin_sup_weak, wcol, wn, k + 1, self._novel_mask)
         dy = ops.zeros((lin_sup.shape[0], self.group.kp), grad_dtype, lin_sup.device)
         ops.softmax_ce(scores, 0, k + 1, roi_cls, dy=dy, dcol0=self.col_cls, loss_out=loss_out[0:1])
-        ops.box_reg_loss(lin_sup, self.col_bbox, k, roi_cls, rois5, roi_gt, self.bbox_reg_weights, dy=dy, dcol0=self.col_bbox,
+        bbox, bcol = self.add_weak_deltas(lin_sup, self.col_bbox, lin_sup_weak), (0 if self.regression_branch else self.col_bbox)
+        ops.box_reg_loss(bbox, bcol, k, roi_cls, rois5, roi_gt, self.bbox_reg_weights, dy=dy, dcol0=self.col_bbox,
                          loss_out=loss_out[1:2], loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)
         return dy, scores
+
+    def add_weak_deltas(self, bbox, col0, lin_weak):
+        """fast_rcnn.py:370-374, 426: bbox[:, col0 : col0 + 4K] + regression_branch_bbox(x_weak) as an fp32 [R, 4K] buffer, `bbox` itself
+        without the branch. The weak head is evaluated under no_grad there (:388-392), so d(loss)/d(sum) is d(loss)/d(bbox_pred_delta):
+        the loss kernel writes it into the bbox_pred_delta columns of dy and nothing else changes. The add is unit_sup_scores, whose
+        `delta + mean of ONE block of weak columns` over 4K columns is exactly this sum (s / 1.0f is s): no new kernel, no ATen launch."""
+        if not self.regression_branch:
+            return bbox
+        return ops.sup_scores(bbox, col0, lin_weak, self.weak_detector_head.col_reg_bbox, 1, 4 * self.num_classes)
 
 
     # ---- plugin surface: the reference's signatures (fast_rcnn.py:384,435,455). Forward values only (see WeakDetectorOutputsBase).
@@ -332,13 +481,15 @@ class SupervisedDetectorOutputsBase(nn.Module):
                     sm = sm[None].expand(r, -1, -1)
                 sims.append(sm.float().contiguous() if sm is not None else None)
             ft = self.group_ft.fwd(xc) if self.finetune else None
-            scores, bbox = ops.transfer_predictions(lin_sup, self.col_cls, self.col_bbox, k, lin_w, wh.col_oicr[0], wh.oicr_iter, sims[0],
+            wcol, wn = wh.score_cols
+            scores, bbox = ops.transfer_predictions(lin_sup, self.col_cls, self.col_bbox, k, lin_w, wcol, wn, sims[0],
                                                     sims[1], t["base"], t["novel"], t["role"], t["slot"], ft=ft, fccol0=self.col_cls,
                                                     fbcol0=self.col_bbox)
+            bbox = self.add_weak_deltas(bbox, 0, lin_w)          # after the base -> novel transfer of the supervised deltas (:414-426)
         else:
-            scores = ops.sup_scores(lin_sup, self.col_cls, lin_w, wh.col_oicr[0], wh.oicr_iter, k + 1,
-                                    t["novel_mask"] if self.training else None)
-            bbox = lin_sup[:, self.col_bbox:self.col_bbox + 4 * k]
+            wcol, wn = wh.score_cols
+            scores = ops.sup_scores(lin_sup, self.col_cls, lin_w, wcol, wn, k + 1, t["novel_mask"] if self.training else None)
+            bbox = self.add_weak_deltas(lin_sup, self.col_bbox, lin_w) if self.regression_branch else lin_sup[:, self.col_bbox:self.col_bbox + 4 * k]
         weak_ret = None
         if x_weak is not None:
             weak_ret, _ = wh(x_weak)
@@ -382,27 +533,8 @@ class SupervisedDetectorOutputsBase(nn.Module):
         softmax, drop bg, apply_deltas, clip, score > thresh, per-class NMS, top-k) on the device"""
         if tta:
             raise NotImplementedError("TTA is outside the hot path (SURVEY.md section 2)")
-        from .inference import pack_proposal_instances
-        from ..structures import Boxes, Instances
         scores, bbox = predictions
-        dev, k = scores.device, self.num_classes
-        props, pcount = pack_proposal_instances(proposals, dev)
-        n, rcap = props.shape[0], props.shape[1]
-        probs = ops.softmax_rows(scores.float().contiguous(), k + 1)
-        pp = torch.zeros((n * rcap, k + 1), dtype=torch.float32, device=dev)
-        bb = torch.zeros((n * rcap, 4 * k), dtype=torch.float32, device=dev)
-        o = 0
-        for i, p in enumerate(proposals):      # ragged -> fixed slots (API boundary; the fused eval path never leaves fixed slots)
-            pp[i * rcap:i * rcap + len(p)], bb[i * rcap:i * rcap + len(p)] = probs[o:o + len(p)], bbox[o:o + len(p)].float()
-            o += len(p)
-        hw = torch.tensor([p.image_size for p in proposals], dtype=torch.float32).to(dev)
-        boxes, sc, cls, roi, cnt = ops.detections(pp, bb, props, pcount, hw, self.bbox_reg_weights, self.test_score_thresh,
-                                                  self.test_nms_thresh, self.test_topk_per_image)
-        res, inds = [], []
-        for i, c in enumerate(cnt.tolist()):
-            res.append(Instances(proposals[i].image_size, pred_boxes=Boxes(boxes[i, :c]), scores=sc[i, :c], pred_classes=cls[i, :c].long()))
-            inds.append(roi[i, :c].long())
-        return res, inds
+        return _detect(self, ops.softmax_rows(scores.float().contiguous(), self.num_classes + 1), bbox, proposals)
 
 
 @FAST_RCNN_REGISTRY.register()

@@ -8,6 +8,17 @@ from .. import ops
 from ..structures import Boxes, Instances
 
 
+class UnsupportedConfig(ValueError, AssertionError):
+    """a configuration this project refuses. A ValueError, as a bad value of a config key is; also an AssertionError, which is what every other
+    refusal at construction of the predictors raises (`assert ...` in modeling/fast_rcnn.py) and what callers of build_model therefore catch"""
+
+
+VISUAL_WITH_REGRESSION_BRANCH = (
+    "a \"visual\" term in MODEL.ROI_HEADS.FINETUNE_TERMS together with WEAK_DETECTOR.REGRESSION_BRANCH is not supported: the reference's "
+    "get_similarity_matrices reads evaluation(...)[0][0] as a list of refinement streams (roi_heads.py:250-252), which under the switch is one "
+    "[R, K+1] tensor whose mean's index_select(1, ...) fails. Use [\"lingual\"] or [] for every head")
+
+
 def _rh(m):
     return getattr(m, "roi_heads", m)
 
@@ -46,6 +57,8 @@ def similarity_dict(model, lin_weak_on_box, want_ctx=False):
     sims, out = {}, {}
     for head, terms in rh.terms.items():
         key = ("lingual" in terms, "visual" in terms)
+        if key[1] and wh.regression_branch:
+            raise UnsupportedConfig(VISUAL_WITH_REGRESSION_BRANCH)
         if key not in sims:
             sims[key] = ops.similarity(lin_weak_on_box, wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1, t["base"], lingual,
                                        t["novel"].numel(), rh.visual_threshold, key[0], key[1])
@@ -82,9 +95,10 @@ def roi_heads_inference(rh, feat, props, pcount, hw, dt, with_mask=True, want_si
     sims = similarity_dict(rh, lin_w_box)
     t = class_roles(rh)
     ft = bp.group_ft.fwd(box_feat) if getattr(bp, "finetune", False) else None
-    scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_w_sup, wh.col_oicr[0], wh.oicr_iter,
+    scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_w_sup, *wh.score_cols,
                                             sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"], ft=ft,
                                             fccol0=bp.col_cls, fbcol0=bp.col_bbox)
+    bbox = bp.add_weak_deltas(bbox, 0, lin_w_sup)          # REGRESSION_BRANCH: + the weak deltas, after the transfer (fast_rcnn.py:414-426)
     probs = ops.softmax_rows(scores, rh.num_classes + 1)
     boxes, sc, cls, roi, cnt = ops.detections(probs, bbox, props, pcount, hw, bp.bbox_reg_weights, bp.test_score_thresh,
                                               bp.test_nms_thresh, bp.test_topk_per_image)

@@ -223,7 +223,9 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         wh = bp.weak_detector_head
         fused("heads", "roi_heads.box_predictor.weak_detector_head",
               [("classifier_stream", wh.classifier_stream), ("detection_stream", wh.detection_stream)] +
-              [(f"oicr_predictors.{i}", m) for i, m in enumerate(wh.oicr_predictors)])
+              [(f"oicr_predictors.{i}", m) for i, m in enumerate(wh.oicr_predictors)] +
+              ([("regression_branch_cls", wh.regression_branch_cls), ("regression_branch_bbox", wh.regression_branch_bbox)]
+               if wh.regression_branch else []))          # (the order of wh.group: the head's fused master weight stays one view)
 
         def stage(tag, prefix, st):
             buckets = {}
@@ -383,7 +385,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         n_sup, n_weak = batch.n_sup, batch.n_weak
         n_img = n_sup + n_weak
         c.n_sup, c.n_weak = n_sup, n_weak
-        c.losses = ops.zeros(len(LOSS_NAMES), torch.float32, self.device)
+        c.losses = ops.zeros(len(self.loss_names), torch.float32, self.device)
         c.metrics = None
         if self.collect_metrics:
             c.metrics = ops.zeros(step_metrics.SIZE, torch.int32, self.device)          # (the library's own fill: a recorded call, replayed with the step)
@@ -682,8 +684,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 c.lin_w_box = wh.group.fwd(c.box_feat)
                 sims, lingual, keys = similarity_dict(self, c.lin_w_box, want_ctx=True)
                 t = class_roles(self)
-                c.scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak_sup, wh.col_oicr[0],
-                                                          wh.oicr_iter, sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"],
+                c.scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak_sup, *wh.score_cols,
+                                                          sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"],
                                                           ft=lin_ft, fccol0=bp.col_cls, fbcol0=bp.col_bbox)
                 c.dy_sup = bp.ft_losses(c.scores, bbox, c.roi_cls, c.rois[:rs], c.roi_gt, c.losses[0:2], dt)
                 if c.metrics is not None:          # on the transferred logits, as the reference's FastRCNNOutputs sees them
@@ -706,9 +708,11 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                         ops.metrics_fastrcnn(c.scores, 0, rh.num_classes + 1, c.roi_cls, c.metrics[step_metrics.FAST_RCNN:step_metrics.FAST_RCNN + 5])
                 c.sup_losses_on_head_stream = sup_side is not None
         if rw > 0:
+            # REGRESSION_BRANCH: the weak head's two further losses take the slots behind LOSS_NAMES (self.loss_names)
+            reg_kw = dict(reg_loss_out=c.losses[len(LOSS_NAMES):]) if bp.weak_detector_head.regression_branch else {}
             c.dy_weak = bp.weak_detector_head.fused_losses(lin_weak_w, c.rois[rs:], c.weak_valid, s // rh.weak_divisor, n_weak,
                                                      batch.multihot, c.losses[2:6], dt,
-                                                     side_stream=self._rpn_stream if self._streams_on() else None)
+                                                     side_stream=self._rpn_stream if self._streams_on() else None, **reg_kw)
         if sup_side is not None:
             torch.cuda.current_stream().wait_stream(sup_side)
         return c
@@ -977,7 +981,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         rh, bp = self.roi_heads, self.roi_heads.box_predictor
         mods = []
         if c.dy_weak is None:
-            mods += [bp.weak_detector_head.classifier_stream, bp.weak_detector_head.detection_stream] + list(bp.weak_detector_head.oicr_predictors)
+            mods += list(bp.weak_detector_head.group.members)          # both streams, the refinement predictors, the regression branch
             if rh.weak_box_head is not None:
                 mods.append(rh.weak_box_head)
         if c.dy_sup is None:
@@ -1019,6 +1023,14 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             if p.requires_grad and p.grad is None:
                 p.grad = st._view(st.grads, e["offset"], p)
 
+    @property
+    def loss_names(self):
+        """the slots of the step's loss vector: LOSS_NAMES, then the weak head's loss_regression_cls / loss_regression_bbox when
+        WEAK_DETECTOR.REGRESSION_BRANCH is on (a model without the switch keeps its nine slots)"""
+        from .fast_rcnn import REGRESSION_LOSSES
+        wh = getattr(getattr(self.roi_heads, "box_predictor", None), "weak_detector_head", None)
+        return LOSS_NAMES + (REGRESSION_LOSSES if getattr(wh, "regression_branch", False) else [])
+
     # ------------------------------------------------------------------ plugin surface
     def forward(self, batched_inputs, weak_batched_inputs=None, return_similarity=False, train_only_weak=False):
         """rcnn.py:433. (Tests that need reproducible sampling set `model.next_perms = {...}` before the call: the explicit-
@@ -1032,12 +1044,13 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         step = self.forward_train(batch, perms)
         if self._anchor is None or self._anchor.device != self.device:
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
-        names = LOSS_NAMES if batch.n_weak > 0 else [n for n in LOSS_NAMES if not (n.startswith("loss_oicr") or n == "loss_im_cls")]
+        all_names = self.loss_names
+        names = all_names if batch.n_weak > 0 else [n for n in LOSS_NAMES if not (n.startswith("loss_oicr") or n == "loss_im_cls")]
         if step.mask_ctx is None:
             names = [n for n in names if n != "loss_mask"]
-        used = torch.tensor([n in names for n in LOSS_NAMES], device=self.device)
+        used = torch.tensor([n in names for n in all_names], device=self.device)
         lv = _StepFn.apply(self._anchor, self, step, step.losses, used)
-        return {n: lv[LOSS_NAMES.index(n)] for n in names}
+        return {n: lv[all_names.index(n)] for n in names}
 
     def train_step(self, batch, optimizer=None, perms=None):
         """forward + backward (+ optimizer) without going through torch.autograd; returns the device loss vector."""

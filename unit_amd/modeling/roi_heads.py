@@ -60,12 +60,19 @@ class WSROIHeadNoMeta(nn.Module):
         self._base_classes = list(cfg.DATASETS.FEWSHOT.BASE_CLASSES_ID)
         self._novel_classes = list(cfg.DATASETS.FEWSHOT.NOVEL_CLASSES_ID)
         self.terms = {"cls": list(rh.FINETUNE_TERMS.CLASSIFIER), "bbox": list(rh.FINETUNE_TERMS.BBOX)}
+        self._check_terms()
         self.visual_threshold = rh.VISUAL_ATTENTION_HEAD.VISUAL_SIMILARITY_THRESHOLD
         thing_classes = thing_classes or (VOC_CLASSES if self.num_classes == 20 else _COCO[: self.num_classes])
         self._coco_indexer = coco_indexer(thing_classes)
         for name, p in self.named_parameters():   # roi_heads.py:166-171
             if any(layer == name.split(".")[0] for layer in cfg.MODEL.FREEZE_LAYERS.ROI_HEADS):
                 p.requires_grad = False
+
+    def _check_terms(self):
+        """refused at construction rather than at the first evaluation: every eval pass computes the similarity matrices of all heads"""
+        if self.box_predictor.weak_detector_head.regression_branch and any("visual" in t for t in self.terms.values()):
+            from .inference import VISUAL_WITH_REGRESSION_BRANCH, UnsupportedConfig
+            raise UnsupportedConfig(VISUAL_WITH_REGRESSION_BRANCH)
 
     def prepare(self, dtype, version):
         self.box_head.prepare(dtype, version)
@@ -222,6 +229,7 @@ class WSROIHeadNoMetaWithMask(WSROIHeadNoMeta):
             self.mask_head = ROI_MASK_HEAD_REGISTRY.get(cfg.MODEL.ROI_MASK_HEAD.NAME)(cfg, ShapeSpec(channels=self.box_head.out_channels,
                                                                                                       height=7, width=7))
         self.terms["seg"] = list(cfg.MODEL.ROI_HEADS.FINETUNE_TERMS.MASK)
+        self._check_terms()
 
     def prepare(self, dtype, version):
         super().prepare(dtype, version)

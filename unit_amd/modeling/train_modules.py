@@ -174,6 +174,7 @@ def rpn_forward_train(module, images, features, gt_instances):
 # ------------------------------------------------------------------------------------------------ ROI heads
 # WSROIHeadNoMeta roi_heads.py:496-591, WSROIHeadFineTune :595-644, WSROIHeadNoMetaWithMask :712-822, WSROIHeadWithMaskFineTune :826-952
 HEAD_LOSSES = ["loss_cls", "loss_box_reg", "loss_im_cls", "loss_oicr_1", "loss_oicr_2", "loss_oicr_3", "loss_mask"]
+REG_SLOTS = slice(len(HEAD_LOSSES), len(HEAD_LOSSES) + 2)          # loss_regression_cls / loss_regression_bbox (REGRESSION_BRANCH only)
 
 
 class _HeadsFn(torch.autograd.Function):
@@ -234,7 +235,7 @@ class _HeadsFn(torch.autograd.Function):
             box_feat, weak_ctx, rows = wfeat_all[:rs], None, None
         lin_sup = bp.group.fwd(box_feat)
         lin_weak = wh.group.fwd(wfeat_all)
-        losses = ops.zeros(len(HEAD_LOSSES), torch.float32, dev)
+        losses = ops.zeros(len(HEAD_LOSSES) + (2 if wh.regression_branch else 0), torch.float32, dev)
         st = {"mask_ctx": None, "dsim_mask": None, "sel": None}
 
         def run_mask(sim=None, roles=None):          # rcnn.forward_train run_mask (roi_heads.py:691-710 / :888-906)
@@ -271,7 +272,7 @@ class _HeadsFn(torch.autograd.Function):
             lin_w_box = wh.group.fwd(box_feat)
             sims, lingual, keys = similarity_dict(rh, lin_w_box, want_ctx=True)
             t = class_roles(rh)
-            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak[:rs], wh.col_oicr[0], wh.oicr_iter,
+            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak[:rs], *wh.score_cols,
                                                     sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"], ft=lin_ft,
                                                     fccol0=bp.col_cls, fbcol0=bp.col_bbox)
             dy_sup = bp.ft_losses(scores, bbox, roi_cls, rois[:rs], roi_gt, losses[0:2], dtype)
@@ -285,7 +286,8 @@ class _HeadsFn(torch.autograd.Function):
             multihot = torch.zeros((n_weak, rh.num_classes), dtype=torch.uint8)
             for i, c in enumerate(io["weak_targets"]):
                 multihot[i, c.long().cpu()] = 1          # torch.unique(gt_classes) (weak_detector_fast_rcnn.py:203)
-            dy_weak = wh.fused_losses(lin_weak[rs:], rois[rs:], weak_valid, sw, n_weak, multihot.to(dev), losses[2:6], dtype)
+            reg_kw = dict(reg_loss_out=losses[REG_SLOTS]) if wh.regression_branch else {}
+            dy_weak = wh.fused_losses(lin_weak[rs:], rois[rs:], weak_valid, sw, n_weak, multihot.to(dev), losses[2:6], dtype, **reg_kw)
         io["rois"], io["roi_cls"], io["mask_on"] = rois, roi_cls, st["mask_ctx"] is not None
         ctx.rh, ctx.geo = rh, (n_sup, n_weak, rs, rw, feat.shape, feat_w.shape if has_weak else None, multi, rows, box_trainable, ft, dtype)
         ctx.saved = (box_feat, wfeat_all, box_ctx, weak_ctx, dy_sup, dy_weak, rois, ft_ctx, st)
@@ -300,6 +302,8 @@ class _HeadsFn(torch.autograd.Function):
         # only the losses that were handed out carry a weight: without a weak batch (rcnn.py:456-459, :644 -- weak_features None) the caller
         # got the supervised losses, the weak slots of the vector are unused zeros whose incoming gradient is 0
         used = [0, 1] + ([2, 3, 4, 5] if dy_weak is not None else []) + ([6] if st["mask_ctx"] is not None else [])
+        if dy_weak is not None and wh.regression_branch:
+            used += [REG_SLOTS.start, REG_SLOTS.start + 1]
         _check_unit_weights(gl[used], type(rh).__name__)
         need_dx = box_ctx is not None
         g = gw = None
@@ -362,6 +366,11 @@ def roi_heads_forward_train(rh, features, proposals, targets, weak_features, wea
     io = {"proposals": proposals, "targets": targets, "weak_proposals": weak_proposals if has_weak else None, "weak_targets": weak_targets}
     lv = _HeadsFn.apply(f, fw, rh, io)
     names = HEAD_LOSSES[:2] + (HEAD_LOSSES[2:6] if has_weak else []) + (["loss_mask"] if io["mask_on"] else [])
+    all_names = HEAD_LOSSES
+    if rh.box_predictor.weak_detector_head.regression_branch:
+        from .fast_rcnn import REGRESSION_LOSSES
+        all_names = HEAD_LOSSES + REGRESSION_LOSSES
+        names = names + (REGRESSION_LOSSES if has_weak else [])
     rh._last_train_io = io
     s = rh.batch_size_per_image
     sampled = []
@@ -369,7 +378,7 @@ def roi_heads_forward_train(rh, features, proposals, targets, weak_features, wea
         r = io["rois"][i * s:(i + 1) * s]
         c = io["roi_cls"][i * s:(i + 1) * s]
         sampled.append(Instances(p.image_size, proposal_boxes=Boxes(r[:, 1:]), gt_classes=c))
-    return sampled, {n: lv[HEAD_LOSSES.index(n)] for n in names}
+    return sampled, {n: lv[all_names.index(n)] for n in names}
 
 
 # ------------------------------------------------------------------------------------------------ predictors on their own
@@ -406,12 +415,14 @@ class _SupPredictFn(torch.autograd.Function):
                     sm = sm[None].expand(r, -1, -1)
                 sims.append(sm.detach().float().contiguous() if sm is not None else None)
             lin_ft = bp.group_ft.fwd(xc)
-            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, k, lin_w, wh.col_oicr[0], wh.oicr_iter, sims[0], sims[1],
+            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, k, lin_w, *wh.score_cols, sims[0], sims[1],
                                                     t["base"], t["novel"], t["role"], t["slot"], ft=lin_ft, fccol0=bp.col_cls, fbcol0=bp.col_bbox)
             ctx.saved = (xc, lin_sup, sims)
         else:
-            scores = ops.sup_scores(lin_sup, bp.col_cls, lin_w, wh.col_oicr[0], wh.oicr_iter, k + 1, t["novel_mask"])
-            bbox = lin_sup[:, bp.col_bbox:bp.col_bbox + 4 * k].contiguous()
+            scores = ops.sup_scores(lin_sup, bp.col_cls, lin_w, *wh.score_cols, k + 1, t["novel_mask"])
+            # REGRESSION_BRANCH: + regression_branch_bbox(x_weak), evaluated under no_grad in the reference (:388-392, 426) -- the backward
+            # below hands the incoming gradient to the bbox_pred_delta columns alone either way
+            bbox = bp.add_weak_deltas(lin_sup, bp.col_bbox, lin_w) if bp.regression_branch else lin_sup[:, bp.col_bbox:bp.col_bbox + 4 * k].contiguous()
             ctx.saved = (xc, None, None)
         return scores, bbox
 
@@ -483,12 +494,15 @@ class _SupLossFn(torch.autograd.Function):
 
 
 class _WeakLossFn(torch.autograd.Function):
-    """WeakDetectorOutputsBase.losses (weak_detector_fast_rcnn.py:189-255) on the fused layout lin [B * S, kp] -> [loss_im_cls, loss_oicr_1..n]"""
+    """WeakDetectorOutputsBase.losses (weak_detector_fast_rcnn.py:189-255) on the fused layout lin [B * S, kp] -> [loss_im_cls, loss_oicr_1..n]
+    (+ [loss_regression_cls, loss_regression_bbox] under REGRESSION_BRANCH)"""
 
     @staticmethod
     def forward(ctx, lin, wh, meta):
-        loss = ops.zeros(1 + wh.oicr_iter, torch.float32, lin.device)
-        dy = wh.fused_losses(lin.detach().float().contiguous(), meta["rois5"], meta["valid"], meta["s"], meta["b"], meta["multihot"], loss, torch.float32)
+        loss = ops.zeros(wh.n_losses, torch.float32, lin.device)
+        reg_kw = dict(reg_loss_out=loss[1 + wh.oicr_iter:]) if wh.regression_branch else {}
+        dy = wh.fused_losses(lin.detach().float().contiguous(), meta["rois5"], meta["valid"], meta["s"], meta["b"], meta["multihot"], loss, torch.float32,
+                             **reg_kw)
         ctx.wh, ctx.dy = wh, dy
         return loss
 
@@ -501,4 +515,8 @@ class _WeakLossFn(torch.autograd.Function):
         if wh.weak_detector_type != "PCL":          # PCLFunction.backward (pcl_loss.py:40-61) ignores grad_output: under TYPE "PCL" the
             for i, c in enumerate(wh.col_oicr):     # refinement columns keep the gradient the loss kernel emitted, whatever weight arrives
                 dy[:, c:c + k + 1] *= g[1 + i]
+        if wh.regression_branch:          # FastRCNNOutputsRegression's two losses are ordinary autograd losses under either TYPE
+            n = 1 + wh.oicr_iter
+            dy[:, wh.col_reg_cls:wh.col_reg_cls + k + 1] *= g[n]
+            dy[:, wh.col_reg_bbox:wh.col_reg_bbox + 4 * k] *= g[n + 1]
         return dy, None, None

@@ -1408,13 +1408,33 @@ def wsddn_mil(streams, ccol0, dcol0, k, valid, s, b, multihot, cls_temp, det_tem
     return loss, xr
 
 
-def oicr_targets(src, col0, mode, k, rois5, valid, s, b, multihot, fg_thresh=0.5, bg_thresh=0.1):
+def oicr_targets(src, col0, mode, k, rois5, valid, s, b, multihot, fg_thresh=0.5, bg_thresh=0.1, want_boxes=False):
+    """want_boxes (the regression branch): -> (labels, weights, gt_boxes [b * s, 4]), the box of the pseudo-GT each row was matched to
+    (unit_oicr_targets_ex); the plain form keeps its own export, so a model without the branch launches what it always did"""
     rtot = rois5.shape[0]
     labels = torch.empty((rtot,), dtype=torch.int32, device=src.device)
     weights = torch.empty((rtot,), dtype=torch.float32, device=src.device)
-    check(lib().unit_oicr_targets(_p(src), src.shape[1], col0, mode, k, _p(rois5), _p(valid), s, b, _p(multihot), float(fg_thresh),
-                                  float(bg_thresh), _p(labels), _p(weights), _s()), "oicr_targets")
-    return labels, weights
+    args = (_p(src), src.shape[1], col0, mode, k, _p(rois5), _p(valid), s, b, _p(multihot), float(fg_thresh), float(bg_thresh), _p(labels),
+            _p(weights))
+    if not want_boxes:
+        check(lib().unit_oicr_targets(*args, _s()), "oicr_targets")
+        return labels, weights
+    if rtot != b * s or valid.numel() != rtot or src.shape[0] != rtot:
+        raise ValueError("oicr_targets: src, rois5 and valid need b * s rows")
+    boxes = torch.empty((rtot, 4), dtype=torch.float32, device=src.device)
+    check(lib().unit_oicr_targets_ex(*args, _p(boxes), _s()), "oicr_targets_ex")
+    return labels, weights, boxes
+
+
+def softmax_mean(logits, col0, step, n, k, valid=None):
+    """oicr_mean_scores (weak_detector_fast_rcnn.py:248) -> [R, k + 1]: the mean over `n` refinement streams (columns col0 + t * step) of
+    their row softmaxes; rows with valid < 0 are zeros (include/unit_hip.h: unit_softmax_mean)"""
+    r, ld = logits.shape
+    if valid is not None and valid.numel() != r:
+        raise ValueError("softmax_mean: valid needs one entry per row")
+    out = torch.empty((r, k + 1), dtype=torch.float32, device=logits.device)
+    check(lib().unit_softmax_mean(_p(logits), ld, col0, step, n, k, _p(valid), _p(out), k + 1, r, _s()), "softmax_mean")
+    return out
 
 
 def pcl_loss(logits, col0, k, valid, s, b, labels, cls_weights, gt_assign, pc_count, pc_img_cls_weights, pc_probs, n_pc, dy=None, dcol0=0,
@@ -1446,10 +1466,12 @@ def kmeans_draws():
 
 
 def pcl_targets(src, col0, mode, nxt, ncol0, nmode, k, rois5, valid, s, b, multihot, ldc, n_streams=1, step=0, nstep=0, fg_thresh=0.5,
-                bg_thresh=0.1, graph_iou_thresh=0.4, max_pc_num=5):
+                bg_thresh=0.1, graph_iou_thresh=0.4, max_pc_num=5, want_boxes=False):
     """PCL targets of `n_streams` refinement streams (include/unit_hip.h: unit_pcl_targets) -> dict of unit_pcl_loss's inputs, every entry
     with a leading stream axis: labels / cls_weights / gt_assign [n_streams, b * s], pc_labels / pc_count / pc_img_cls_weights / pc_probs
     [n_streams, b, ldc], n_pc [n_streams, b]. Stream t reads src columns col0 + t * step and nxt columns ncol0 + t * nstep.
+    want_boxes (the regression branch): additionally gt_boxes [n_streams, b * s, 4], the centre box each row was matched to
+    (unit_pcl_targets_ex); the plain form keeps its own export.
     Nothing here is a stock torch operator: torch.empty only reserves memory (the step's pool under ReplayedStep)."""
     dev, rows = src.device, b * s
     if rois5.shape[0] != rows or valid.numel() != rows or src.shape[0] != rows or nxt.shape[0] != rows:
@@ -1463,11 +1485,15 @@ def pcl_targets(src, col0, mode, nxt, ncol0, nmode, k, rois5, valid, s, b, multi
                pc_probs=f32(n_streams, b, ldc))
     nb = lib().unit_workspace_bytes_pcl_targets(b, s, n_streams)
     ws = torch.empty((nb,), dtype=torch.uint8, device=dev)
-    check(lib().unit_pcl_targets(_p(src), src.shape[1], col0, mode, step, _p(nxt), nxt.shape[1], ncol0, nmode, nstep, k, _p(rois5), _p(valid),
-                                 s, b, n_streams, _p(multihot), float(fg_thresh), float(bg_thresh), float(graph_iou_thresh), int(max_pc_num),
-                                 _p(out["labels"]), _p(out["cls_weights"]), _p(out["gt_assign"]), _p(out["n_pc"]), _p(out["pc_labels"]),
-                                 _p(out["pc_count"]), _p(out["pc_img_cls_weights"]), _p(out["pc_probs"]), ldc, _p(ws), nb, _s()),
-          "pcl_targets")
+    args = (_p(src), src.shape[1], col0, mode, step, _p(nxt), nxt.shape[1], ncol0, nmode, nstep, k, _p(rois5), _p(valid),
+            s, b, n_streams, _p(multihot), float(fg_thresh), float(bg_thresh), float(graph_iou_thresh), int(max_pc_num),
+            _p(out["labels"]), _p(out["cls_weights"]), _p(out["gt_assign"]), _p(out["n_pc"]), _p(out["pc_labels"]),
+            _p(out["pc_count"]), _p(out["pc_img_cls_weights"]), _p(out["pc_probs"]), ldc)
+    if want_boxes:
+        out["gt_boxes"] = f32(n_streams, rows, 4)
+        check(lib().unit_pcl_targets_ex(*args, _p(out["gt_boxes"]), _p(ws), nb, _s()), "pcl_targets_ex")
+    else:
+        check(lib().unit_pcl_targets(*args, _p(ws), nb, _s()), "pcl_targets")
     return out
 
 
