@@ -460,6 +460,28 @@ int unit_transfer_predictions_bwd(const void* dy, int dy_dtype, int ldd, int dcc
 int unit_similarity_bwd(const float* lin_weak, int ld, int col0, int n_oicr, int ncls, const int* base_dev, int n_base,
                         const float* lingual, int n_novel, float visual_threshold, int use_lingual, int use_visual, const float* dsim,
                         void* dlin, int dlin_dtype, int ldl, int dcol0, int R, void* stream);
+/* ---- a14, the remaining similarity terms (csrc/similarity.hip; modeling/similarity_terms.py holds the plan of a term list) ----
+ * unit_similarity_static: the per-model part under "Sum", roi_heads.py:270-305 -- A [n_novel][n_base] = 0 + weight * softmax(lingual)
+ * (:271-272) + weight * TopK (:273-283) + weight * WTopK (:284-294) + weight * LSDA (:295-305); a k of 0 leaves the term out. The class
+ * weights are rows row0 + s * ncls + c (s < n_oicr) of the fp32 master matrix of the weak head's fused Linear, D columns, leading
+ * dimension ld, averaged over the streams per element. One launch, one workgroup per novel class. */
+int unit_similarity_static(const float* w_master, int ld, int row0, int n_oicr, int ncls, int D, const int* base_dev, int n_base,
+                           const int* novel_dev, int n_novel, const float* lingual, float weight, int use_lingual, int k_topk, int k_wtopk,
+                           int k_lsda, float* A, void* stream);
+/* unit_similarity_ex: sim [R][n_novel][n_base] from A and the per-RoI term, roi_heads.py:306-324 -- VisualK (k_visual > 0, :306-315:
+ * softmax over the K foreground columns of the mean refinement logits, base columns renormalised, the k largest divided by their sum)
+ * or 'visual' (use_visual, :250-257, :316-317; never both), then Average (:318-320), the row normalisation with its 1e-9 clamp or None's
+ * zero (:321-324); product: "Product" (:325-332), which is softmax(0) = 1 / n_base whatever the terms. With use_visual and / or a
+ * lingual-only A and nothing else it gives unit_similarity's bits. */
+int unit_similarity_ex(const float* lin_weak, int ld, int col0, int n_oicr, int ncls, const int* base_dev, int n_base, const float* A,
+                       int n_novel, float visual_threshold, float weight, int use_visual, int k_visual, int average, int none, int product,
+                       float* sim, int R, void* stream);
+/* unit_similarity_bwd_ex: dsim -> the refinement logit columns of dlin (zero-filled first, 1 / n_oicr per stream, bf16 or fp32) through
+ * the normalisation (:322), the top-k scatter and its sum (:311-314), the base renormalisation (:310) and the softmax (:308) -- the
+ * reference computes the matrices with grad in the fine-tune heads' training forward (:852). Zeros without a per-RoI term. */
+int unit_similarity_bwd_ex(const float* lin_weak, int ld, int col0, int n_oicr, int ncls, const int* base_dev, int n_base, const float* A,
+                           int n_novel, float visual_threshold, float weight, int use_visual, int k_visual, int average, int none,
+                           int product, const float* dsim, void* dlin, int dlin_dtype, int ldl, int dcol0, int R, void* stream);
 /* ---- a15 detections: fast_rcnn.py:455-468 -> detectron2 fast_rcnn_inference; rcnn.py:411-429 detector_postprocess ---- */
 int unit_softmax_rows(const float* x, int ld, int ncls, float* y, int ldy, int R, void* stream);
 int unit_detection_candidates(const float* probs, int ldp, const float* deltas, int ldd, const float* props, const int* pcount, int B,

@@ -1,5 +1,6 @@
 // detect.hip -- base->novel similarity transfer (fine-tune / eval predictor) and the detection post-processing.
-//   a14  WSROIHead.get_similarity_matrices  modeling/roi_heads/roi_heads.py:245-336  ('lingual' + 'visual', "Sum")
+//   a14  WSROIHead.get_similarity_matrices  modeling/roi_heads/roi_heads.py:245-336  ('lingual' + 'visual', "Sum"; every other term and
+//        "Product": similarity.hip)
 //        SupervisedDetectorOutputs*.forward transfer   modeling/roi_heads/fast_rcnn.py:401-423, 504-523
 //   a15  SupervisedDetectorOutputsBase.inference -> detectron2 fast_rcnn_inference (fast_rcnn.py:455-468)
 #include "common.h"

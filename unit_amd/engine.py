@@ -284,6 +284,14 @@ class GraphedStep:
         return ent[2]
 
 
+REPLAY_FINETUNE_TRAINABLE_BOX_HEAD = (
+    "engine.ReplayedStep does not take a fine-tune step whose box head trains (the COCO segm fine-tune yaml): that step makes part of its work "
+    "with stock torch operators, which a call list does not hold -- rcnn.backward_train sums three input gradients (`dbox + ... + ...`) and adds "
+    "the mask head's similarity gradient (`torch.zeros`, `dsim += dsim_mask`), and the mask head's [predictor | predictor_delta] group, one "
+    "member frozen and one trainable, is not adjacent in the flat store, so LinearGroup.prepare gathers its master matrix with torch copies "
+    "every step; a replayed list would read the recorded step's copies. Run this configuration eagerly or under GraphedStep")
+
+
 class ReplayedStep(GraphedStep):
     """One whole training step as a CALL LIST walked in C (csrc/replay.hip, _lib.Recorder): the second step of a batch key runs eagerly
     with every enqueueing C-ABI call and every event record / wait noted down -- function address + argument words -- and every later step
@@ -304,6 +312,9 @@ class ReplayedStep(GraphedStep):
         slot -- a core burnt per rank for nothing (measured: 2 busy threads per process, bench.py `host_cpu_ms_per_step`). With a bound, the host
         sleeps on a blocking HIP event (hipEventBlockingSync: an interrupt, not a poll) until the step `run_ahead` steps back has finished."""
         super().__init__(model, optimizer, warmup_steps=warmup_steps, buckets=buckets, per_bucket=True)
+        rh = getattr(model, "roi_heads", None)
+        if rh is not None and getattr(rh.box_predictor, "finetune", False) and any(p.requires_grad for p in rh.box_head.parameters()):
+            raise NotImplementedError(REPLAY_FINETUNE_TRAINABLE_BOX_HEAD)
         self.plans = {}          # key -> (CallList, static PackedBatch, losses tensor, (metrics vector | None, its image count))
         self.mempool = None
         import collections

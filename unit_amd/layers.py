@@ -515,7 +515,7 @@ class LinearGroup:
         self.k = c
         self.kp = (c + 7) // 8 * 8
         self._prep_key = None
-        self.wf = self.wd = self.bias = None
+        self.wf = self.wd = self.bias = self.w32 = self._gathered = None
 
     def _fused_views(self, attr):
         """(weight_view [kp,cin] or None, bias_view [k] or None) if the members are contiguous in memory."""
@@ -546,12 +546,16 @@ class LinearGroup:
         w, b = self._fused_views("data")
         if w is None:
             dev = self.members[0].weight.device
-            w = torch.zeros((self.kp, self.cin), dtype=torch.float32, device=dev)
+            # the gathered master matrix keeps its address across re-preparations, like wf / wd: a recorded unit_similarity_static reads it
+            if self._gathered is None or self._gathered.device != dev:
+                self._gathered = torch.zeros((self.kp, self.cin), dtype=torch.float32, device=dev)
+            w = self._gathered          # (the pad rows stay zero: only the members' rows are rewritten)
             b = torch.zeros((self.k,), dtype=torch.float32, device=dev)
             for m, c in zip(self.members, self.cols):
                 w[c:c + m.out_features].copy_(m.weight.data.reshape(m.out_features, self.cin))
                 b[c:c + m.out_features].copy_(m.bias.data)
         self.bias = b
+        self.w32 = w          # the fp32 master rows (a view of the members' storage, or the gathered copy): similarity terms over class weights
         self.wf, self.wd = ops.weight_prep(w, None, self.kp, 1, 1, self.cin, self.cin, dtype, w_fwd=self.wf if self.wf is not None and self.wf.dtype == dtype else None,
                                            w_dgrad=self.wd if self.wd is not None and self.wd.dtype == dtype else None)
         self._prep_key = key

@@ -47,25 +47,48 @@ def class_roles(model):
 
 
 def similarity_dict(model, lin_weak_on_box, want_ctx=False):
-    """WSROIHead.get_similarity_matrices roi_heads.py:245-336 ('Sum' combination of 'lingual' / 'visual' terms) -> {head: [R,n,b]}
-    (want_ctx: also the lingual matrix and the (use_lingual, use_visual) key of every head, for the backward)"""
+    """WSROIHead.get_similarity_matrices roi_heads.py:245-336 -> {head: [R,n,b]}. Every head's term list goes by its plan
+    (similarity_terms.parse_terms): 'lingual' / 'visual' alone under "Sum" take unit_similarity as ever, every other plan the static part
+    (unit_similarity_static) and unit_similarity_ex.
+    (want_ctx: also the lingual matrix and, for the backward, {head: (plan, static part or None)})"""
     rh = _rh(model)
     bp = rh.box_predictor
+    plans = rh.term_plans()          # (parsed at construction; re-parsed, and refused if need be, when the lists were edited on the built model)
     t = class_roles(rh)
     wh = bp.weak_detector_head
     lingual = ops.embedding_similarity(bp.embeddings.weight, t["emb_novel"], t["emb_base"])       # fast_rcnn.py:376-382
-    sims, out = {}, {}
-    for head, terms in rh.terms.items():
-        key = ("lingual" in terms, "visual" in terms)
-        if key[1] and wh.regression_branch:
-            raise UnsupportedConfig(VISUAL_WITH_REGRESSION_BRANCH)
-        if key not in sims:
-            sims[key] = ops.similarity(lin_weak_on_box, wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1, t["base"], lingual,
-                                       t["novel"].numel(), rh.visual_threshold, key[0], key[1])
-        out[head] = sims[key]
+    oicr = (wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1)
+    sims, statics, out, ctx = {}, {}, {}, {}
+    for head, plan in plans.items():
+        static = None
+        if not plan.plain:
+            sk = "constant" if plan.constant else plan.static_key
+            if sk not in statics:          # Average / None / "Product" never read the static part: any [n, b] buffer stands in, no launch
+                statics[sk] = lingual if plan.constant else ops.similarity_static(wh.group.w32, *oicr, t["base"], t["novel"], lingual, plan)
+            static = statics[sk]
+        if plan not in sims:
+            if plan.plain:
+                sims[plan] = ops.similarity(lin_weak_on_box, *oicr, t["base"], lingual, t["novel"].numel(), rh.visual_threshold, *plan.key)
+            else:
+                sims[plan] = ops.similarity_ex(lin_weak_on_box, *oicr, t["base"], static, rh.visual_threshold, plan)
+        out[head] = sims[plan]
+        ctx[head] = (plan, static)
     if want_ctx:
-        return out, lingual, {h: ("lingual" in tm, "visual" in tm) for h, tm in rh.terms.items()}
+        return out, lingual, ctx
     return out
+
+
+def similarity_backward(rh, lin_weak_on_box, lingual, ctx, dsim, grad_dtype):
+    """d(loss)/d(similarity matrix) -> d(loss)/d(the weak head's logits on the box features), by the plan that `similarity_dict(..., want_ctx=True)`
+    returned (rcnn.backward_train and train_modules._HeadsFn.backward: the two sites where the box head trains under the fine-tune heads)"""
+    assert len(set(p for p, _ in ctx.values())) == 1, "fine-tune backward: one similarity matrix for all heads (equal FINETUNE_TERMS)"
+    plan, static = next(iter(ctx.values()))
+    t = class_roles(rh)
+    wh = rh.box_predictor.weak_detector_head
+    oicr = (wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1)
+    if plan.plain:
+        return ops.similarity_bwd(lin_weak_on_box, *oicr, t["base"], lingual, t["novel"].numel(), rh.visual_threshold, *plan.key, dsim, grad_dtype)
+    return ops.similarity_bwd_ex(lin_weak_on_box, *oicr, t["base"], static, rh.visual_threshold, plan, dsim, grad_dtype)
 
 
 def similarity_matrices(model, lin_weak_on_box):

@@ -768,16 +768,14 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             # into the box head's features.
             dbox = bp.group_ft.bwd(c.box_feat, c.dy_sup, need_dx=box_trainable)
             if box_trainable:
+                from .inference import similarity_backward
                 lin_sup, sims, lingual, keys, t = c.ft_ctx
-                assert len(set(keys.values())) == 1, "fine-tune backward: one similarity matrix for all heads (equal FINETUNE_TERMS)"
-                ul, uv = next(iter(keys.values()))
                 wh = bp.weak_detector_head
                 dlin, dsim = ops.transfer_predictions_bwd(c.dy_sup, bp.col_cls, bp.col_bbox, lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes,
                                                           sims["cls"], sims["bbox"], t, bp.group.kp)
                 if c.dsim_mask is not None:
                     dsim += c.dsim_mask
-                dlin_w = ops.similarity_bwd(c.lin_w_box, wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1, t["base"], lingual,
-                                            t["novel"].numel(), rh.visual_threshold, ul, uv, dsim, dt)
+                dlin_w = similarity_backward(rh, c.lin_w_box, lingual, keys, dsim, dt)          # (one matrix for all heads: asserted there)
                 dbox = dbox + bp.group.bwd(c.box_feat, dlin, need_dx=True) + wh.group.bwd(c.box_feat, dlin_w, need_dx=True)
         elif c.dy_sup is not None:
             # The supervised losses ran on the head stream, beside the (three times longer) weak loss chain on this one. With

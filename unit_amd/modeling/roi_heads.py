@@ -60,6 +60,7 @@ class WSROIHeadNoMeta(nn.Module):
         self._base_classes = list(cfg.DATASETS.FEWSHOT.BASE_CLASSES_ID)
         self._novel_classes = list(cfg.DATASETS.FEWSHOT.NOVEL_CLASSES_ID)
         self.terms = {"cls": list(rh.FINETUNE_TERMS.CLASSIFIER), "bbox": list(rh.FINETUNE_TERMS.BBOX)}
+        self.similarity_combination = rh.VISUAL_ATTENTION_HEAD.SIMILARITY_COMBINATION          # roi_heads.py:186
         self._check_terms()
         self.visual_threshold = rh.VISUAL_ATTENTION_HEAD.VISUAL_SIMILARITY_THRESHOLD
         thing_classes = thing_classes or (VOC_CLASSES if self.num_classes == 20 else _COCO[: self.num_classes])
@@ -70,9 +71,23 @@ class WSROIHeadNoMeta(nn.Module):
 
     def _check_terms(self):
         """refused at construction rather than at the first evaluation: every eval pass computes the similarity matrices of all heads"""
-        if self.box_predictor.weak_detector_head.regression_branch and any("visual" in t for t in self.terms.values()):
-            from .inference import VISUAL_WITH_REGRESSION_BRANCH, UnsupportedConfig
-            raise UnsupportedConfig(VISUAL_WITH_REGRESSION_BRANCH)
+        self.term_plans()
+
+    def term_plans(self):
+        """{head: similarity_terms.Plan}, or UnsupportedConfig naming the rule that refuses a list. Parsed at construction; parsed again only
+        when a list, the combination or the regression branch was changed on the built model"""
+        from .similarity_terms import check_regression_branch, parse_terms
+        reg = self.box_predictor.weak_detector_head.regression_branch
+        key = (self.similarity_combination, reg, tuple((h, tuple(t)) for h, t in self.terms.items()))
+        cached = getattr(self, "_term_plans", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        plans = {h: parse_terms(t, self.similarity_combination, len(self._base_classes)) for h, t in self.terms.items()}
+        if reg:
+            for p in plans.values():
+                check_regression_branch(p)
+        self._term_plans = (key, plans)
+        return plans
 
     def prepare(self, dtype, version):
         self.box_head.prepare(dtype, version)

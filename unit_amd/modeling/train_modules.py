@@ -313,15 +313,13 @@ class _HeadsFn(torch.autograd.Function):
                 if need_dx:
                     # ... through the frozen delta heads incl. the base -> novel transfer, and the similarity (computed WITH grad in the
                     # reference, roi_heads.py:852), into the box head's features (rcnn.backward_train)
+                    from .inference import similarity_backward
                     lin_sup, sims, lingual, keys, t, lin_w_box = ft_ctx
-                    assert len(set(keys.values())) == 1, "fine-tune backward: one similarity matrix for all heads (equal FINETUNE_TERMS)"
-                    ul, uv = next(iter(keys.values()))
                     dlin, dsim = ops.transfer_predictions_bwd(dy_sup, bp.col_cls, bp.col_bbox, lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes,
                                                               sims["cls"], sims["bbox"], t, bp.group.kp)
                     if st["dsim_mask"] is not None:
                         dsim += st["dsim_mask"]
-                    dlin_w = ops.similarity_bwd(lin_w_box, wh.col_oicr[0], wh.oicr_iter, rh.num_classes + 1, t["base"], lingual,
-                                                t["novel"].numel(), rh.visual_threshold, ul, uv, dsim, dtype)
+                    dlin_w = similarity_backward(rh, lin_w_box, lingual, keys, dsim, dtype)          # (one matrix for all heads: asserted there)
                     dbox = dbox + bp.group.bwd(box_feat, dlin, need_dx=True) + wh.group.bwd(box_feat, dlin_w, need_dx=True)
             else:
                 dbox = bp.group.bwd(box_feat, dy_sup, need_dx=True)

@@ -1549,6 +1549,51 @@ def similarity_bwd(lin_weak, col0, n_oicr, ncls, base_dev, lingual, n_novel, vis
     return dlin
 
 
+def similarity_static(w_master, row0, n_oicr, ncls, base_dev, novel_dev, lingual, plan):
+    """the per-model part of a term plan (modeling/similarity_terms.Plan) -> A [n_novel, n_base] = w (softmax(lingual) + TopK + WTopK + LSDA);
+    w_master: fp32 [rows, D] master matrix of the weak head's fused Linear, its refinement streams at rows row0 + s * ncls + class"""
+    if w_master is None:
+        raise ValueError("similarity_static: the weak head's fused Linear has no master matrix yet (LinearGroup.prepare)")
+    if w_master.dtype != torch.float32 or w_master.dim() != 2 or w_master.stride(1) != 1:
+        raise ValueError("similarity_static: the class weights must be a row-major fp32 matrix")
+    nb, nn_ = base_dev.numel(), novel_dev.numel()
+    if row0 < 0 or row0 + n_oicr * ncls > w_master.shape[0]:
+        raise ValueError("similarity_static: the refinement streams' rows leave the master matrix")
+    a = torch.empty((nn_, nb), dtype=torch.float32, device=w_master.device)
+    check(lib().unit_similarity_static(_p(w_master), w_master.stride(0), row0, n_oicr, ncls, w_master.shape[1], _p(base_dev), nb, _p(novel_dev),
+                                       nn_, _p(lingual), float(plan.weight), int(plan.lingual), plan.topk, plan.wtopk, plan.lsda, _p(a), _s()),
+          "similarity_static")
+    return a
+
+
+def _plan_words(plan, visual_threshold):
+    return (float(visual_threshold), float(plan.weight), int(plan.visual), plan.visualk, int(plan.average), int(plan.zero), int(plan.product))
+
+
+def similarity_ex(lin_weak, col0, n_oicr, ncls, base_dev, a, visual_threshold, plan):
+    """sim [R, n_novel, n_base] of a term plan from its static part `a` and the weak head's logits on the box features"""
+    r = lin_weak.shape[0]
+    nn_, nb = a.shape
+    if col0 < 0 or col0 + n_oicr * ncls > lin_weak.shape[1]:
+        raise ValueError("similarity_ex: the refinement logit columns leave the row")
+    sim = torch.empty((r, nn_, nb), dtype=torch.float32, device=lin_weak.device)
+    check(lib().unit_similarity_ex(_p(lin_weak), lin_weak.shape[1], col0, n_oicr, ncls, _p(base_dev), nb, _p(a), nn_,
+                                   *_plan_words(plan, visual_threshold), _p(sim), r, _s()), "similarity_ex")
+    return sim
+
+
+def similarity_bwd_ex(lin_weak, col0, n_oicr, ncls, base_dev, a, visual_threshold, plan, dsim, grad_dtype):
+    """backward of `similarity_ex` -> d(loss)/d(lin_weak) [R, ld] (zeros for a plan without a per-RoI term)"""
+    r, ld = lin_weak.shape
+    nn_, nb = a.shape
+    if tuple(dsim.shape) != (r, nn_, nb) or dsim.dtype != torch.float32:
+        raise ValueError("similarity_bwd_ex: dsim must be fp32 [R, n_novel, n_base]")
+    dlin = torch.empty((r, ld), dtype=grad_dtype, device=lin_weak.device)
+    check(lib().unit_similarity_bwd_ex(_p(lin_weak), ld, col0, n_oicr, ncls, _p(base_dev), nb, _p(a), nn_, *_plan_words(plan, visual_threshold),
+                                       _p(dsim), _p(dlin), dt(grad_dtype), ld, col0, r, _s()), "similarity_bwd_ex")
+    return dlin
+
+
 def softmax_rows(x, ncls):
     y = torch.empty((x.shape[0], ncls), dtype=torch.float32, device=x.device)
     check(lib().unit_softmax_rows(_p(x), x.shape[1], ncls, _p(y), ncls, x.shape[0], _s()), "softmax_rows")
