@@ -522,6 +522,8 @@ int unit_mask_targets(const unsigned char* gt_masks, int Mcap, int Hm, int Wm, c
  * Arithmetic = pycocotools' rleFrPoly on the box-relative, M / side scaled vertices (fp64 on the device); cls outside [0, K): zeros. */
 int unit_mask_targets_polygon(const double* poly_xy, const int* poly_start, const int* inst_start, const int* image_inst0,
                               const float* rois5, const int* gt_index, const int* cls, int K, int S, int M, unsigned char* out, void* stream);
+/* unit_mask_bce_loss, unit_mask_bce_loss_ft and unit_mask_probs read logits fp32 [S][M/2][M/2][4][ldk] (pixel (Y, X) at
+ * [Y/2][X/2][(Y&1)*2 + (X&1)]): the mask side M must be even and >= 2, anything else is UNIT_ERR_ARG before a launch. */
 int unit_mask_bce_loss(const float* logits, int K, int ldk, const int* cls, const unsigned char* targets, int S, int M, float gscale,
                        float* loss, void* dlogits, int d_dtype, void* stream);
 /* training form of the fine-tune mask head (mask_head.py:74-93 with similarity['seg'][fg], roi_heads.py:888-906): gt-class logit =

@@ -126,6 +126,7 @@ __global__ void mask_loss_kernel(const float* __restrict__ logits, int K, int ld
 }
 extern "C" int unit_mask_bce_loss(const float* logits, int K, int ldk, const int* cls, const unsigned char* targets, int S, int M,
                                   float gscale, float* loss, void* dlogits, int d_dtype, void* stream) {
+  UNIT_CHECK_ARG(M >= 2 && M % 2 == 0, "mask_bce_loss: mask side must be even (logits are [S][M/2][M/2][4][ldk])");
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(loss, 0, sizeof(float), st);
   if (S == 0) return UNIT_OK;
@@ -213,6 +214,7 @@ extern "C" int unit_mask_bce_loss_ft(const float* logits, int K, int ldk, int de
                                      const float* sim, const int* sim_rows, const int* base_dev, int n_base, int n_novel,
                                      const int8_t* role_dev, const int* slot_dev, int S, int M, float gscale, float* loss, void* dlogits,
                                      int d_dtype, float* dsim, void* stream) {
+  UNIT_CHECK_ARG(M >= 2 && M % 2 == 0, "mask_bce_loss_ft: mask side must be even (logits are [S][M/2][M/2][4][ldk])");
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(loss, 0, sizeof(float), st);
   if (S == 0) return UNIT_OK;
@@ -258,6 +260,7 @@ __global__ void mask_probs_kernel(const float* __restrict__ logits, int K, int l
 }
 extern "C" int unit_mask_probs(const float* logits, int K, int ldk, int delta_col0, const int* cls, const float* sim, const int* base_dev,
                                int n_base, int n_novel, const int8_t* role_dev, const int* slot_dev, int S, int M, float* out, void* stream) {
+  UNIT_CHECK_ARG(M >= 2 && M % 2 == 0, "mask_probs: mask side must be even (logits are [S][M/2][M/2][4][ldk])");
   if (S == 0) return UNIT_OK;
   mask_probs_kernel<<<cdiv((long)S * M * M, 256), 256, 0, (hipStream_t)stream>>>(logits, K, ldk, delta_col0, cls, sim, base_dev, n_base, n_novel,
                                                                                 role_dev, slot_dev, S, M, out);
