@@ -256,7 +256,8 @@ __device__ __forceinline__ f32x4 box_decode1(f32x4 d, f32x4 b, f32x4 wt, float c
   float w = b[2] - b[0], h = b[3] - b[1];
   float cx = b[0] + 0.5f * w, cy = b[1] + 0.5f * h;
   float dx = d[0] / wt[0], dy = d[1] / wt[1];
-  float dw = fminf(d[2] / wt[2], clampv), dh = fminf(d[3] / wt[3], clampv);
+  float dw = d[2] / wt[2], dh = d[3] / wt[3];
+  dw = dw > clampv ? clampv : dw; dh = dh > clampv ? clampv : dh;   // torch.clamp(max=) keeps a NaN dw / dh; fminf would turn it into clampv
   float pcx = dx * w + cx, pcy = dy * h + cy;
   float pw = expf(dw) * w, ph = expf(dh) * h;
   f32x4 o = {pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
