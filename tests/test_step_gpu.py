@@ -676,3 +676,37 @@ def test_dual_gemm_weight_concatenations_follow_the_optimizer(dev):
     torch.cuda.synchronize()
     assert check() == 2
     assert torch.isfinite(l0).all() and torch.isfinite(l32).all() and torch.isfinite(l1).all()
+
+
+def _gen_step_plan():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(__file__), "golden", "gen_step_plan_parent.py")
+    spec = importlib.util.spec_from_file_location("gen_step_plan_parent", path)
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    return gen
+
+
+@pytest.mark.parametrize("case", _gen_step_plan().CASES)
+def test_step_plan_is_the_parent_commits(dev, case):
+    """the forms of the step plan that test_box_loss_gpu's equal-size 2 + 2 replay does not reach -- a ragged batch as one ops.Ragged pass, as
+    two sequential passes, a step without weak images -- record, name for name, in order AND stream for
+    stream (the role of the stream every call, event record and event wait was issued on), what the commit before the step's settled A/B
+    switches were retired recorded (tests/golden/step_plan_parent.json, written there by gen_step_plan_parent.py), and compute its six loss
+    vectors bit for bit; the replayed steps equal the eager ones in losses and in the flat parameters after six steps."""
+    import json
+    gen = _gen_step_plan()
+    with open(gen.OUT) as f:
+        parent = json.load(f)[case]
+    r = gen.run_case(case)
+    assert r["stats"] == {"eager": 2, "captured": 1, "replayed": 3}
+    assert r["form"] == {"ragged": (True, True), "two_pass": (True, False)}.get(case, (False, False))
+    assert len(r["names"]) == len(parent["names"]) and r["names"] == parent["names"]
+    moved = [(k, n, a, b) for k, (n, a, b) in enumerate(zip(r["names"], r["streams"], parent["streams"])) if a != b]
+    assert len(r["streams"]) == len(parent["streams"]) and not moved, moved[:8]
+    assert {"main", "wgrad"} <= set(r["streams"]) and "none" not in r["streams"]          # the roles were resolved
+    for k, (a, b) in enumerate(zip(r["replayed"], r["eager"])):
+        assert torch.isfinite(a).all() and torch.equal(a, b), (k, a.tolist(), b.tolist())
+    assert [a.tolist() for a in r["replayed"]] == parent["losses"]
+    assert torch.equal(r["m_replayed"].store.params, r["m_eager"].store.params)

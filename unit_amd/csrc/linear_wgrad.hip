@@ -159,12 +159,12 @@ __global__ void __launch_bounds__(256) linear_wgrad_sum_kernel(const float* __re
   }
 }
 
+constexpr int LINW_WORKGROUPS = 128;          // launch size aimed at (64 / 128 / 256 / 512 tried: profiles/r04_exp_linear_wgrad.txt)
+
 int pick_splits(int R, int C) {
-  // ~128 workgroups (tools/linear_wgrad_ab.py: 64 / 128 / 256 / 512 tried), at least 2 stages of 32 rows per split, at most 32 splits
-  static int target = -1;
-  if (target < 0) { const char* e = getenv("UNIT_LINW_WORKGROUPS"); target = e ? atoi(e) : 128; }      // tuning knob
+  // ~LINW_WORKGROUPS workgroups, at least 2 stages of 32 rows per split, at most 32 splits
   int slices = C / 128;
-  int s = (target + slices - 1) / slices;
+  int s = (LINW_WORKGROUPS + slices - 1) / slices;
   int max_by_rows = R / 64; if (max_by_rows < 1) max_by_rows = 1;
   if (s > max_by_rows) s = max_by_rows;
   if (s > 32) s = 32;

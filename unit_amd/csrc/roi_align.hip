@@ -257,9 +257,7 @@ extern "C" int unit_roi_align_fwd(const void* feat_nhwc, int dtype, int N, int H
   int threads = ((C / 8 + 63) / 64) * 64;
   long blocks = (long)R * out_size * out_size;
   hipStream_t st = (hipStream_t)stream;
-  static int row_form = -1;
-  if (row_form < 0) { const char* e = getenv("UNIT_ROI_ROW_FORM"); row_form = e ? atoi(e) : 1; }
-  if (row_form && dtype == UNIT_BF16 && threads <= 256) {
+  if (dtype == UNIT_BF16 && threads <= 256) {
     roi_align_fwd_row_kernel<bf16_t><<<(long)R * out_size, threads, 0, st>>>((const bf16_t*)feat_nhwc, H, W, C, rois, roi_count_dev, pooled_size, out_size,
                                                                            bin_step, spatial_scale, sampling_ratio, aligned, (bf16_t*)out);
     UNIT_LAUNCH_CHECK();

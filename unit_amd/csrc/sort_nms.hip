@@ -224,8 +224,8 @@ extern "C" int unit_sort_desc_stable(const float* src, long batch_stride, int ld
 //      the (start, end) of every group goes to a table. Nc >= min(topk, n) candidates; non-candidates sort after them.
 //  (2) group_rank_kernel (64 candidates per workgroup): rank(i) = start of its group + #{j in the group : cand_j < cand_i} on the
 //      unique 64-bit composites (ties broken by ascending original index = the stable order); writes out[rank]. The groups
-//      hold a few hundred candidates (16 bins per octave of score), so this is ~1/50 of the all-pairs count it replaces
-//      (rank_sort_kernel, kept for reference: 85 us for 4 x 12 000). Entries beyond Nc get index -1 / score -inf.
+//      hold a few hundred candidates (16 bins per octave of score), so this is ~1/50 of the all-pairs count it replaced
+//      (85 us for 4 x 12 000). Entries beyond Nc get index -1 / score -inf.
 // ---------------------------------------------------------------------------------------------------
 #define SEL_BINS 8192
 __global__ void __launch_bounds__(1024) topk_select_kernel(const float* __restrict__ src, long bstride, int ld, int A, int col0, int n,
@@ -292,7 +292,7 @@ __global__ void __launch_bounds__(256) group_rank_kernel(const unsigned long lon
                                                          int ld, int A, int col0, float* __restrict__ out_keys, int* __restrict__ out_idx) {
   // 64 consecutive (bin-grouped) candidates per workgroup; they are compared with the candidates of THEIR groups only: everything
   // before the first group is smaller, everything behind the last one larger. Tiles of 1024 composites through LDS, the four
-  // waves take a quarter of each tile (rank_sort_kernel's loop over a sub-range).
+  // waves take a quarter of each tile.
   __builtin_amdgcn_s_setprio(2);   // proposal chain = critical path of the step
   __shared__ unsigned long long tile[1024];
   __shared__ int part[4][64];
@@ -334,44 +334,6 @@ __global__ void __launch_bounds__(256) group_rank_kernel(const unsigned long lon
   }
 }
 
-__global__ void __launch_bounds__(256) rank_sort_kernel(const unsigned long long* __restrict__ cand, const int* __restrict__ cand_count,
-                                                        int n, const float* __restrict__ src, long bstride, int ld, int A, int col0,
-                                                        float* __restrict__ out_keys, int* __restrict__ out_idx) {
-  __builtin_amdgcn_s_setprio(2);   // proposal chain = critical path of the step; the other streams' kernels are throughput work
-  __shared__ unsigned long long tile[1024];
-  __shared__ int part[4][64];
-  int b = blockIdx.y;
-  int nc = cand_count[b];
-  int i0 = blockIdx.x * 64;
-  if (threadIdx.x < 64 && i0 + (int)threadIdx.x >= nc && i0 + (int)threadIdx.x < n) {      // (group_rank_kernel)
-    out_keys[(size_t)b * n + i0 + threadIdx.x] = -__builtin_inff();
-    out_idx[(size_t)b * n + i0 + threadIdx.x] = -1;
-  }
-  if (i0 >= nc) return;
-  int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const unsigned long long* c = cand + (size_t)b * n;
-  unsigned long long mine = (i0 + lane < nc) ? c[i0 + lane] : ~0ull;
-  int cnt = 0;
-  for (int j0 = 0; j0 < nc; j0 += 1024) {
-    __syncthreads();
-#pragma unroll
-    for (int t = tid; t < 1024; t += 256) tile[t] = (j0 + t < nc) ? c[j0 + t] : ~0ull;   // ~0 is never < anything
-    __syncthreads();
-    const unsigned long long* tq = tile + wid * 256;
-#pragma unroll 16
-    for (int j = 0; j < 256; ++j) cnt += (tq[j] < mine) ? 1 : 0;
-  }
-  part[wid][lane] = cnt;
-  __syncthreads();
-  if (wid == 0 && i0 + lane < nc) {
-    int r = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-    int id = (int)(unsigned)(mine & 0xffffffffull);
-    int pix = id / A, a = id - pix * A;
-    out_keys[(size_t)b * n + r] = src[(size_t)b * bstride + (size_t)pix * ld + col0 + a];   // original bits (keeps -0.0)
-    out_idx[(size_t)b * n + r] = id;
-  }
-}
-
 extern "C" int unit_sort_desc_stable_topk(const float* src, long batch_stride, int ld, int A, int col0, int B, int n, int topk,
                                           float min_exclusive, float* out_keys, int* out_idx, void* workspace, size_t workspace_bytes,
                                           void* stream) {
@@ -384,11 +346,7 @@ extern "C" int unit_sort_desc_stable_topk(const float* src, long batch_stride, i
   hipStream_t st = (hipStream_t)stream;
   topk_select_kernel<<<B, 1024, 0, st>>>(src, batch_stride, ld, A, col0, n, topk, min_exclusive, cand, cand_count, groups);
   UNIT_LAUNCH_CHECK();
-  // UNIT_RANK_ALLPAIRS=1: the all-pairs rank count this replaced (A/B, tools/nms_bench.py)
-  static int allpairs = -1;
-  if (allpairs < 0) { const char* e = getenv("UNIT_RANK_ALLPAIRS"); allpairs = e ? atoi(e) : 0; }
-  if (allpairs) rank_sort_kernel<<<dim3((n + 63) / 64, B), 256, 0, st>>>(cand, cand_count, n, src, batch_stride, ld, A, col0, out_keys, out_idx);
-  else group_rank_kernel<<<dim3((n + 63) / 64, B), 256, 0, st>>>(cand, cand_count, groups, n, src, batch_stride, ld, A, col0, out_keys, out_idx);
+  group_rank_kernel<<<dim3((n + 63) / 64, B), 256, 0, st>>>(cand, cand_count, groups, n, src, batch_stride, ld, A, col0, out_keys, out_idx);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }
@@ -545,158 +503,13 @@ __global__ void __launch_bounds__(NMS_SCAN_THREADS) nms_scan_kernel(const float*
   if (tid == 0) keep_count[b] = nkept;
 }
 
-// nms_scan_pf_kernel: the scan for up to 16 384 candidates (nw <= 256 words, one thread per word) with the mask rows
-// PREFETCHED one chunk ahead. In nms_scan_kernel every chunk pays a dependent HBM / Infinity-Cache round trip (~2-3 us)
-// for the rows of the boxes it just kept, on a single CU, with the rest of the chip idle on the critical path of the step
-// (0.8 ms for 4 x 12 000 RPN candidates). Here, while chunk c is being resolved, every thread already loads its word of the
-// rows of chunk c+1's CANDIDATES: the boxes of chunk c+1 not yet removed by chunks < c (a superset of what chunk c+1 can
-// keep, because chunk c can only remove more), first PF = 32 of them, into registers. After chunk c+1 is resolved the kept
-// boxes' rows are already there; kept boxes beyond the 32 prefetched candidates (rare) take the old dependent-load path.
-// Same greedy result, bit for bit.
-#define NMS_PF 32
-#define NMS_PF_MAXKEEP 4096
-__device__ __forceinline__ unsigned long long nms_uniform64(unsigned long long v) {
-  return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
-         (unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
-}
-
-__global__ void __launch_bounds__(256) nms_scan_pf_kernel(const float* __restrict__ boxes, const float* __restrict__ scores,
-                                                          const int* __restrict__ count, int cap, int nw,
-                                                          const unsigned long long* __restrict__ mask, int max_keep,
-                                                          int* __restrict__ keep_idx, int* __restrict__ keep_count,
-                                                          float* __restrict__ out_boxes, float* __restrict__ out_scores) {
-  // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. wait for the prefetch loads that must stay in flight
-#define NMS_LDS_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
-  __shared__ unsigned long long s_cur, s_kept, s_next;
-  __shared__ int s_nkept;
-  __shared__ int s_keep[NMS_PF_MAXKEEP];                   // kept indices: boxes / scores are gathered after the scan (a load
-                                                          // inside it would wait, in order, for the prefetches behind it)
-  const int b = blockIdx.x;
-  const int n = count ? min(count[b], cap) : cap;
-  const unsigned long long* mk = mask + (size_t)b * cap * nw;
-  const int tid = threadIdx.x;
-  unsigned long long removed = 0;  // word `tid` of the removed bitmap
-  int nkept = 0;
-  if (tid == 0) s_nkept = 0;
-  const int nchunks = (n + 63) / 64;
-  // diagonal word (word ch of row ch*64 + lane) of the chunk to resolve next: loaded by EVERY wave, unconditionally and one
-  // chunk ahead like the prefetches (a load under the wave-0 branch would be merged back with a register copy, i.e. waited for)
-  unsigned long long diag_next = mk[(size_t)min(tid & 63, cap - 1) * nw];
-
-  // candidate rows of chunk `ch` (uniform word `cand`): thread t > ch loads word t of the first NMS_PF of them
-  auto prefetch = [&](int ch, unsigned long long cand, unsigned long long (&buf)[NMS_PF]) {
-    unsigned long long w = cand;
-    const int tcl = min(tid, nw - 1);                     // loads are UNCONDITIONAL (clamped, value unused where it does not apply):
-    const int rowmax = cap - 1;                            // exact in-order vmcnt counts let them stay in flight across the chunk
-#pragma unroll
-    for (int u = 0; u < NMS_PF; ++u) {
-      bool have = w != 0ull;
-      int j = have ? __builtin_ctzll(w) : 0;
-      w &= w - 1ull;                                       // 0 stays 0
-      buf[u] = mk[(size_t)min(ch * 64 + j, rowmax) * nw + tcl];
-    }
-  };
-  auto valid_bits = [&](int ch) -> unsigned long long {
-    int lim = n - ch * 64;
-    return lim >= 64 ? ~0ull : (lim <= 0 ? 0ull : ((1ull << lim) - 1ull));
-  };
-
-  // one chunk: CUR / candc = rows prefetched for chunk c and the candidate word they belong to; NXT / candn are filled for c+1.
-  // returns true when max_keep boxes have been kept
-  auto step = [&](int c, unsigned long long (&CUR)[NMS_PF], unsigned long long candc, unsigned long long (&NXT)[NMS_PF],
-                  unsigned long long& candn) -> bool {
-    if (tid == c) s_cur = removed;
-    if (tid == c + 1) s_next = removed;                    // still without the rows of chunk c: a superset of chunk c+1's survivors
-    NMS_LDS_BARRIER();
-    candn = (c + 1 < nchunks) ? (~nms_uniform64(s_next) & valid_bits(c + 1)) : 0ull;
-    const unsigned long long diag_cur = diag_next;
-    diag_next = mk[(size_t)min((c + 1) * 64 + (tid & 63), cap - 1) * nw + min(c + 1, nw - 1)];
-    prefetch(c + 1, candn, NXT);
-    if (tid < 64) {
-      int i = c * 64 + tid;
-      unsigned long long diag = i < n ? diag_cur : 0ull;
-      // the 64-step dependency chain runs on the SCALAR unit (v_readlane with a uniform lane index, s_or / s_bitcmp)
-      unsigned dlo_v = (unsigned)diag, dhi_v = (unsigned)(diag >> 32);
-      unsigned long long cur = nms_uniform64(s_cur);
-      unsigned long long kept = 0;
-      int cnt = __builtin_amdgcn_readfirstlane(s_nkept);
-      int lim = min(64, n - c * 64);
-      // visit only the boxes that survive: the next alive bit is kept and its diagonal word (bits above it only) kills others
-      unsigned long long alive = ~cur & (lim >= 64 ? ~0ull : ((1ull << lim) - 1ull));
-      while (alive != 0ull && cnt < max_keep) {
-        int j = __builtin_ctzll(alive);
-        unsigned long long dj = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane(dhi_v, j) << 32) |
-                                (unsigned)__builtin_amdgcn_readlane(dlo_v, j);
-        kept |= 1ull << j;
-        alive &= ~(dj | (1ull << j));
-        cnt++;
-      }
-      if (tid == 0) { s_kept = kept; s_nkept = cnt; }
-      if ((kept >> tid) & 1ull) {
-        int rank = nkept + __popcll(kept & ((1ull << tid) - 1ull));
-        keep_idx[(size_t)b * max_keep + rank] = i;
-        s_keep[rank] = i;
-      }
-    }
-    NMS_LDS_BARRIER();
-    unsigned long long kept = nms_uniform64(s_kept);
-    nkept = s_nkept;
-    if (nkept >= max_keep) return true;
-    if (tid < nw && tid > c) {
-      unsigned long long w = candc;
-#pragma unroll
-      for (int u = 0; u < NMS_PF; ++u) {
-        if (w != 0ull) {
-          int j = __builtin_ctzll(w);
-          w &= w - 1ull;
-          if ((kept >> j) & 1ull) { removed |= CUR[u]; kept &= ~(1ull << j); }
-        }
-      }
-      // kept boxes that were not among the prefetched candidates
-      const unsigned long long* base = mk + (size_t)(c * 64) * nw + tid;
-      // (one batch = one memory round trip on the chunk's critical path: 32 rows cover 64 kept boxes with the prefetched ones)
-      while (kept) {
-        unsigned long long v[NMS_PF];
-#pragma unroll
-        for (int u = 0; u < NMS_PF; ++u) {
-          v[u] = 0ull;
-          if (kept) {                                      // wave-uniform
-            int j = __ffsll((long long)kept) - 1;
-            kept &= kept - 1;
-            v[u] = base[(size_t)j * nw];
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < NMS_PF; ++u) removed |= v[u];
-      }
-    }
-    return false;
-  };
-
-  unsigned long long bufa[NMS_PF], bufb[NMS_PF];
-  unsigned long long canda = nchunks > 0 ? valid_bits(0) : 0ull, candb = 0ull;
-  prefetch(0, canda, bufa);
-  for (int c = 0; c < nchunks; c += 2) {
-    if (step(c, bufa, canda, bufb, candb)) break;
-    if (c + 1 >= nchunks) break;
-    if (step(c + 1, bufb, candb, bufa, canda)) break;
-  }
-  if (tid == 0) keep_count[b] = nkept;
-  NMS_LDS_BARRIER();
-  for (int r = tid; r < nkept; r += 256) {
-    int i = s_keep[r];
-    size_t o = (size_t)b * max_keep + r;
-    if (out_boxes) *reinterpret_cast<f32x4*>(out_boxes + 4 * o) = *reinterpret_cast<const f32x4*>(boxes + ((size_t)b * cap + i) * 4);
-    if (out_scores) out_scores[o] = scores[(size_t)b * cap + i];
-  }
-#undef NMS_LDS_BARRIER
-}
-
 // ---------------------------------------------------------------------------------------------------
-// nms_scan_dq_kernel: the scan with the serial chain DECOUPLED from the bulk of the row ORs (nw <= 256, max_keep <= 4096).
-// Measured on nms_scan_pf_kernel (clock64 per section, 4 x 12 000 candidates): a 64-box chunk cost 5.7 us = 1 us issuing the
-// candidate prefetch + 2.5 us for the scalar resolve chain (one step per kept box) + 2.2 us for a memory round trip after it
-// (rows of kept boxes that were not prefetched), with every wave of the workgroup in lock-step. Here:
+// nms_scan_dq_kernel: the scan with the serial chain DECOUPLED from the bulk of the row ORs, for up to 16 384 candidates (nw <= 256
+// words) and max_keep <= NMS_DQ_MAXKEEP. In nms_scan_kernel every 64-box chunk pays a dependent HBM / Infinity-Cache round trip (~2-3 us)
+// for the rows of the boxes it just kept, on a single CU, on the critical path of the step: 0.8 ms for 4 x 12 000 RPN candidates. A
+// lock-step scan that prefetched the next chunk's candidate rows (since removed) halved that (346-423 us) and showed where the rest goes
+// (clock64 per section): a chunk cost 5.7 us = 1 us issuing the candidate prefetch + 2.5 us for the scalar resolve chain (one step per kept
+// box) + 2.2 us for a memory round trip after it (rows of kept boxes that were not prefetched), every wave of the workgroup waiting. Here:
 //   wave 0 (resolver) owns the chain and nothing else. Lane i of chunk c has the diagonal word of row 64 c + i (symmetric, from
 //     nms_mask_kernel): the greedy choice inside the chunk is the fixed point of "kept if no kept predecessor overlaps, removed
 //     if one does", found by iterating over the undecided set with two ballots per round (rounds = overlap chain depth, a
@@ -726,6 +539,12 @@ __device__ __forceinline__ i32x4 lds_ld128(const void* p) {
 __device__ __forceinline__ void lds_st32(void* p, int v) { asm volatile("ds_write_b32 %0, %1" :: "v"(lds_addr(p)), "v"(v) : "memory"); }
 __device__ __forceinline__ void lds_st64(void* p, unsigned long long v) { asm volatile("ds_write_b64 %0, %1" :: "v"(lds_addr(p)), "v"(v) : "memory"); }
 
+#define NMS_DQ_MAXKEEP 4096          // kept indices live in LDS until the scan ends
+__device__ __forceinline__ unsigned long long nms_uniform64(unsigned long long v) {
+  return ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) << 32) |
+         (unsigned)__builtin_amdgcn_readfirstlane((unsigned)v);
+}
+
 #define NMS_DQ_D 8
 #ifndef NMS_DQ_RING
 #define NMS_DQ_RING 12
@@ -741,7 +560,7 @@ __global__ void __launch_bounds__(640) nms_scan_dq_kernel(const float* __restric
                                                           const unsigned long long* __restrict__ mask, int max_keep,
                                                           int* __restrict__ keep_idx, int* __restrict__ keep_count,
                                                           float* __restrict__ out_boxes, float* __restrict__ out_scores) {
-  __shared__ int s_keep[NMS_PF_MAXKEEP];
+  __shared__ int s_keep[NMS_DQ_MAXKEEP];
   __shared__ int s_cend[260];                               // s_cend[c + 1] = boxes kept through chunk c
   __shared__ unsigned long long s_bulk[2][256];             // word t: rows applied by the two bulk lanes that own it
   __shared__ unsigned long long s_urg[256 + NMS_DQ_D + 8];  // word t: rows applied by the resolver (chunks t-D .. t-1)
@@ -930,10 +749,8 @@ extern "C" int unit_nms(const float* boxes_sorted, const float* scores_sorted, c
     nms_mask_kernel<<<dim3((nw + 3) / 4, nw, B), 256, 0, st>>>(boxes_sorted, count, cap, nw, thresh, (unsigned long long*)workspace);
     UNIT_LAUNCH_CHECK();
   }
-  // UNIT_NMS_SCAN: 2 (default) decoupled resolver / bulk waves, 1 lock-step scan with prefetch, 0 plain scan
-  static int mode = -1;
-  if (mode < 0) { const char* e = getenv("UNIT_NMS_SCAN"); mode = e ? atoi(e) : 2; }
-  if (nw <= 256 && cap > 0 && max_keep <= NMS_PF_MAXKEEP && mode == 2) {
+  // two forms: the decoupled scan for up to 16 384 candidates and max_keep <= NMS_DQ_MAXKEEP, the plain scan for everything else
+  if (nw <= 256 && cap > 0 && max_keep <= NMS_DQ_MAXKEEP) {
     constexpr int ring_bytes = NMS_DQ_RING * 9 * 64 * 8;
     static bool attr_set = false;
     if (!attr_set) { (void)hipFuncSetAttribute((const void*)nms_scan_dq_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ring_bytes); attr_set = true; }
@@ -942,16 +759,12 @@ extern "C" int unit_nms(const float* boxes_sorted, const float* scores_sorted, c
     UNIT_LAUNCH_CHECK();
     return UNIT_OK;
   }
-  // the other scans write the kept prefix only: index -1, zero box / score behind it
+  // the plain scan writes the kept prefix only: index -1, zero box / score behind it
   (void)hipMemsetAsync(keep_idx, 0xFF, (size_t)B * max_keep * sizeof(int), st);
   if (out_boxes) (void)hipMemsetAsync(out_boxes, 0, (size_t)B * max_keep * 4 * sizeof(float), st);
   if (out_scores) (void)hipMemsetAsync(out_scores, 0, (size_t)B * max_keep * sizeof(float), st);
-  if (nw <= 256 && cap > 0 && max_keep <= NMS_PF_MAXKEEP && mode == 1)
-    nms_scan_pf_kernel<<<B, 256, 0, st>>>(boxes_sorted, scores_sorted, count, cap, nw, (const unsigned long long*)workspace,
-                                          max_keep, keep_idx, keep_count, out_boxes, out_scores);
-  else
-    nms_scan_kernel<<<B, scan_threads, 0, st>>>(boxes_sorted, scores_sorted, count, cap, nw, (const unsigned long long*)workspace,
-                                                max_keep, keep_idx, keep_count, out_boxes, out_scores);
+  nms_scan_kernel<<<B, scan_threads, 0, st>>>(boxes_sorted, scores_sorted, count, cap, nw, (const unsigned long long*)workspace,
+                                              max_keep, keep_idx, keep_count, out_boxes, out_scores);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

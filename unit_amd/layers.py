@@ -10,7 +10,6 @@ Conventions
     a block's bwd returns d(loss)/d(block input) multiplied by (input > 0) when `mask_input` (the input is the
     previous block's post-ReLU output), so masks are fused into the dgrad epilogues and never run as kernels.
 """
-import os
 
 import torch
 from torch import nn
@@ -325,7 +324,7 @@ class BottleneckBlock(nn.Module):
         in bf16 on the stride-2-subsampled RoIAlign output (every conv of the block is then stride 1)"""
         if isinstance(x, ops.Ragged):
             return False
-        return (ops.FUSE_EPILOGUE and ops.FUSE_DUAL and getattr(self, "allow_dual", False) and self.shortcut is not None and st == 1
+        return (ops.FUSE_EPILOGUE and getattr(self, "allow_dual", False) and self.shortcut is not None and st == 1
                 and x.dtype == torch.bfloat16 and x.shape[:3] == y2.shape[:3] and x.shape[0] > 0
                 and ops.conv_ex_supported(x.dtype, self.conv3.cin, self.conv3.cout) and self.shortcut.cin % self.conv3.cin == 0
                 and self.shortcut.cout % self.conv1.cout == 0 and self.conv1.cout % 64 == 0 and self.conv1.cin % 64 == 0)
@@ -336,7 +335,7 @@ class BottleneckBlock(nn.Module):
         prepared weights -- in the training step the optimizer's one multi-tensor launch -- writes the concatenation too. (Until round 4
         a 6 - 10 MB torch.cat per use and per stream: five stock copy kernels per step.) Called by the head's prepare() on the step's
         main stream, before any side stream reads the buffers."""
-        if not (ops.FUSE_EPILOGUE and ops.FUSE_DUAL and getattr(self, "allow_dual", False) and self.shortcut is not None):
+        if not (ops.FUSE_EPILOGUE and getattr(self, "allow_dual", False) and self.shortcut is not None):
             return
         c3, sc, c1 = self.conv3, self.shortcut, self.conv1
         if c3.x3 or sc.x3 or c1.x3:
@@ -448,9 +447,6 @@ class ResStage(nn.Sequential):
         return max(0, n - (k + 1) * self.BUCKET_BLOCKS)
 
 
-_FUSED_STEM = os.environ.get("UNIT_FUSED_STEM", "1") != "0"
-
-
 class BasicStem(nn.Module):
     """detectron2 BasicStem: conv 7x7 s2 p3 + FrozenBN + ReLU + max_pool2d(3,2,1) (frozen: FREEZE_AT >= 1)."""
 
@@ -476,7 +472,7 @@ class BasicStem(nn.Module):
 
     def _fwd_one(self, x, out):
         c = self.conv1
-        if (_FUSED_STEM and x.dtype == torch.bfloat16 and x.is_cuda and c.cout == 64 and x.shape[-1] == 8 and c.wf is not None
+        if (x.dtype == torch.bfloat16 and x.is_cuda and c.cout == 64 and x.shape[-1] == 8 and c.wf is not None
                 and c.wf.dtype == torch.bfloat16 and not c.weight.requires_grad):
             return ops.stem_conv_pool(x, c.wf, c.shift, out=out)          # one persistent launch; the conv output never reaches HBM
         return ops.maxpool3x3s2(c.fwd(x, relu=True), out=out)
@@ -490,9 +486,6 @@ class Linear(_EpochOnLoad):
         self.in_features, self.out_features = cin, cout
         self.weight = nn.Parameter(torch.zeros(cout, cin))
         self.bias = nn.Parameter(torch.zeros(cout))
-
-
-_LINEAR_WGRAD = os.environ.get("UNIT_LINEAR_WGRAD", "1") != "0"     # 0: the predictors' gradients as a 1x1 convolution + column sum (A/B)
 
 
 class LinearGroup:
@@ -589,7 +582,7 @@ class LinearGroup:
                     else:
                         m.bias.grad.add_(tb[c:c + m.out_features])
         elif trainable:
-            if gw is not None and _LINEAR_WGRAD and x2d.dtype == torch.bfloat16 and self.kp <= 128 and self.cin % 128 == 0:
+            if gw is not None and x2d.dtype == torch.bfloat16 and self.kp <= 128 and self.cin % 128 == 0:
                 ops.linear_wgrad(x2d, dy2d, self.k, gw, gb)       # rows [k, kp) of the view belong to other parameters: not written
             elif gw is not None:
                 ops.conv2d_wgrad(x2d.view(r, 1, 1, self.cin), dy2d.view(r, 1, 1, self.kp), self.kp, 1, 1, out=gw.view(self.kp, 1, 1, self.cin))

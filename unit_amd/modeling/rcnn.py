@@ -67,20 +67,6 @@ def pack_gt_masks(ms, dev, mcap):
     return gt_masks.to(dev, non_blocking=True)
 
 
-def _record_tree(obj, streams):
-    """record_stream on every tensor inside nested tuples / lists (ops.ReluBits included): memory allocated under one stream's context
-    that other streams go on using"""
-    if torch.is_tensor(obj):
-        if obj.is_cuda:
-            for s in streams:
-                obj.record_stream(s)
-    elif isinstance(obj, ops.ReluBits):
-        _record_tree(obj.data, streams)
-    elif isinstance(obj, (tuple, list)):
-        for o in obj:
-            _record_tree(o, streams)
-
-
 class _StepFn(torch.autograd.Function):
     """Exposes the explicit plan to torch.autograd as one node: forward has already run, backward runs the backward plan."""
 
@@ -134,23 +120,11 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         # step's preprocessing / frozen stem / res2 run beside it; the main stream joins before its first trainable layer. Whoever reads
         # parameters or gradients on another stream in between calls join_optimizer_tail() first (state_dict() and inference do).
         self.overlap_optimizer_tail = False
-        # ragged supervised / weak batches (forward_train): 0 = the two backbone passes one after the other (default); 1 = the weak batch's backbone
-        # + RPN head on the head stream beside the supervised batch's; 2 = its proposal chain there too. Measured on VOC-shaped batches (bench.py
-        # --shapes voc, 100 steps, two alternating series on one box): 19.57 / 19.77 (0), 19.85 / 19.93 (1), 19.75 / 19.85 ms (2) -- small launches
-        # from two streams interleave, they do not overlap: the concurrent forms stay a switch, sequential is the default.
-        self.two_pass_overlap = int(os.environ.get("UNIT_TWO_PASS_OVERLAP", "0"))
         # ragged supervised / weak batches as ONE backbone + RPN-head pass (ops.Ragged: pointwise layers over the concatenated rows, every
         # other layer as a pair launch, weight gradients with the groups as parts): default; 0 = the two passes of rounds 1-4 (A/B, tests)
         self.ragged_single_pass = os.environ.get("UNIT_RAGGED", "1") != "0"
-        # backward-plan start (profiles/r04_exp_head_backward_start.txt): the RPN 3x3 conv's weight gradient goes out at the end of the
-        # early RPN backward instead of with the heads' bucket; the supervised head's backward follows its losses on the head stream
-        self.early_rpn_wgrad = os.environ.get("UNIT_EARLY_RPN_WGRAD", "1") != "0"
-        self.early_sup_backward = os.environ.get("UNIT_EARLY_SUP_BWD", "1") != "0"
-        self.sup_predictor_on_head_stream = os.environ.get("UNIT_SUP_PRED_ON_HEAD", "1") != "0"
-        self.decoupled_sup_chain = os.environ.get("UNIT_DECOUPLED_SUP_CHAIN", "1") != "0"
         self._tail_pending = None
         self.overlap_streams = True
-        self.split_weak_head = __import__("os").environ.get("UNIT_SPLIT_WEAK", "1") != "0"     # forward plan: weak_box_head as two 1024-RoI passes
         # opt-in (TrainerNoMeta(metrics=True)): the counts behind Detectron2's ten step scalars (unit_amd/metrics.py), added into one int32
         # vector by three small launches inside the step -- no sync; `last_metrics` = the last step's vector (None while the switch is off),
         # `last_metrics_images` = the number of supervised images it counted over
@@ -400,7 +374,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         pad_of = lambda ss: (max(s[0] for s in ss), max(s[1] for s in ss))
         split = n_sup > 0 and n_weak > 0 and pad_of(raw[:n_sup]) != pad_of(raw[n_sup:])
         c.split = split
-        feat_w = head_w = anchors_w = split_props = split_side = feat_r = None
+        c.bb_ctx_w = None          # the weak batch's backbone context: the two-pass form of `split` only
+        feat_w = head_w = anchors_w = feat_r = None
         if not split:
             x, sizes = ops.preprocess_images(batch.images, self._pixel_mean, self._pixel_std, dt, 8, self.normalize_images)
             feat, c.bb_ctx = self.backbone.fwd(x, save=True, before_trainable=self.join_optimizer_tail)
@@ -408,39 +383,14 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             xa, sa = ops.preprocess_images(batch.images[:n_sup], self._pixel_mean, self._pixel_std, dt, 8, self.normalize_images)
             xb, sb = ops.preprocess_images(batch.images[n_sup:], self._pixel_mean, self._pixel_std, dt, 8, self.normalize_images)
             sizes = sa + sb
-            # The two passes are independent until the RoIs are pooled: the weak batch's backbone + RPN head run on the (idle) head stream
-            # beside the supervised batch's. Both are small launches (two images: ~4 800 res4 pixels, 150 - 300 workgroups) that leave most
-            # of the chip empty on their own -- the case real multi-scale batches always hit (bench.py --shapes voc).
-            weak_side = self._head_stream if (self._streams_on() and self.two_pass_overlap) else None
-            split_side = weak_side
-            if weak_side is not None:
-                self.join_optimizer_tail()          # the side pass reads the same weights the pending optimizer tail writes
-                weak_side.wait_stream(torch.cuda.current_stream())
-                xb.record_stream(weak_side)
-                hw_all = self._sizes_on_device(sizes)
-                post = rpn.post_nms_topk[True]
-                if proposals is None and self.two_pass_overlap >= 2:          # both passes write their proposals into one set of tensors
-                    split_props = (torch.empty((n_img, post, 4), dtype=torch.float32, device=self.device),
-                                   torch.empty((n_img, post), dtype=torch.float32, device=self.device),
-                                   torch.empty((n_img,), dtype=torch.int32, device=self.device))
-                    for t in split_props:
-                        t.record_stream(weak_side)
-                with torch.cuda.stream(weak_side):
-                    feat_w, c.bb_ctx_w = self.backbone.fwd(xb, save=True)
-                    head_w, _ = rpn.rpn_head.fwd(feat_w, save=False)          # weak images: proposals only (no RPN loss)
-                    if split_props is not None:          # ... and the weak batch's proposal chain (latency-bound: free beside the supervised pass)
-                        rpn.predict_proposals(head_w, rpn.anchor_generator.grid(feat_w.shape[1], feat_w.shape[2]), hw_all[n_sup:], True,
-                                              out=tuple(t[n_sup:] for t in split_props))
-            if weak_side is None and self.ragged_single_pass:
+            if self.ragged_single_pass:
                 # ONE pass over both groups (ops.Ragged): the reference's two backbone calls (rcnn.py:439, :452) differ only in where each
                 # batch's zero padding starts, which every non-pointwise layer gets from its group's own map size
                 feat_r, c.bb_ctx = self.backbone.fwd([xa, xb], save=True, before_trainable=self.join_optimizer_tail)
-                c.bb_ctx_w = None
                 feat, feat_w = feat_r.groups()
-            else:
+            else:          # the two passes one after the other (side by side on two streams they gained nothing: DESIGN, retired switches)
                 feat, c.bb_ctx = self.backbone.fwd(xa, save=True, before_trainable=self.join_optimizer_tail)          # `feat` = supervised images only
-                if weak_side is None:
-                    feat_w, c.bb_ctx_w = self.backbone.fwd(xb, save=True)
+                feat_w, c.bb_ctx_w = self.backbone.fwd(xb, save=True)
             anchors_w = rpn.anchor_generator.grid(feat_w.shape[1], feat_w.shape[2])
         self.join_optimizer_tail()          # (a fully frozen backbone never called it)
         c.image_sizes = sizes
@@ -480,7 +430,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             head, head_w = (hr.group(i).view(d[0], d[1] * d[2], hr.channels) for i, d in enumerate(hr.dims))
         else:
             head, c.rpn_ctx = rpn.rpn_head.fwd(feat_c, save=True)
-            if split and head_w is None:
+            if split:
                 head_w, _ = rpn.rpn_head.fwd(feat_w_c, save=False)          # weak images: proposals only (no RPN loss)
         c.dhead = None
         c.drpn = None
@@ -505,7 +455,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 c.rpn_losses = c.losses[6:8]          # the branch writes its two slots of the loss vector itself; nobody else touches them
                 rpn_branch()
                 c.drpn = rpn.rpn_head.bwd(c.rpn_ctx, c.dhead, n_sup)
-                if self.early_rpn_wgrad and self.plan is not None:
+                if self.plan is not None:
                     # the 3x3 conv's weight gradient was queued for the heads' grouped launch, which goes out at the first bucket boundary
                     # of the backward plan -- behind everything this stream is given later (the OICR chains) and next to the predictors'
                     # backward. Launched here it runs under RoIAlign (HBM-bound, a few waves per CU) while the chip is half empty.
@@ -523,21 +473,13 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             props, pscores, pcount = proposals
         elif not split:
             props, pscores, pcount = rpn.predict_proposals(head, anchors, hw, True)
-        else:
-            if split_props is None:          # sequential passes (one stream): the same two calls, one set of tensors
-                post = rpn.post_nms_topk[True]
-                split_props = (torch.empty((n_img, post, 4), dtype=torch.float32, device=self.device),
-                               torch.empty((n_img, post), dtype=torch.float32, device=self.device),
-                               torch.empty((n_img,), dtype=torch.int32, device=self.device))
-                rpn.predict_proposals(head_w, anchors_w, hw[n_sup:], True, out=tuple(t[n_sup:] for t in split_props))
+        else:          # two groups of anchors: the same call per group, one set of tensors
+            post = rpn.post_nms_topk[True]
+            props, pscores, pcount = split_props = (torch.empty((n_img, post, 4), dtype=torch.float32, device=self.device),
+                                                    torch.empty((n_img, post), dtype=torch.float32, device=self.device),
+                                                    torch.empty((n_img,), dtype=torch.int32, device=self.device))
+            rpn.predict_proposals(head_w, anchors_w, hw[n_sup:], True, out=tuple(t[n_sup:] for t in split_props))
             rpn.predict_proposals(head, anchors, hw[:n_sup], True, out=tuple(t[:n_sup] for t in split_props))
-            props, pscores, pcount = split_props
-        if split and getattr(c, "bb_ctx_w", None) is not None and split_side is not None:
-            # join the weak batch's side pass (backbone, RPN head, its proposal chain); what it allocated is used -- and later freed -- by work
-            # on the main and weight-gradient streams
-            cur = torch.cuda.current_stream()
-            cur.wait_stream(split_side)
-            _record_tree((feat_w, head_w, c.bb_ctx_w), (cur, self._wgrad_stream))
         c.proposals = (props, pscores, pcount)
         if perm_ready is not None:
             torch.cuda.current_stream().wait_event(perm_ready)
@@ -578,9 +520,10 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 pooled.record_stream(s1)
                 with torch.cuda.stream(s1):
                     c.box_feat, c.box_ctx = rh.box_head.fwd(pooled[:rs], save=box_trainable)
-                if self.split_weak_head and rw > 0:
+                if rw > 0:
                     # three equal chains (box_head, weak_box_head on the supervised RoIs without saving, weak_box_head on the weak RoIs)
                     # on three streams instead of a 1 : 2 pair: they end together and their 392-tile launches pack into whole rounds
+                    # ("three-chain head form")
                     s3 = self._wgrad_stream              # idle during the forward plan
                     s3.wait_stream(main)
                     pooled.record_stream(s3)
@@ -618,6 +561,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         # The sampler emits [fg..., bg...] per image, so the fg RoIs of image i are the first n_fg_i <= 128 slots of its block.
         c.mask_ctx = None
         c.dsim_mask = None
+        c.ft_ctx = None          # (fine-tune step only)
         mh = getattr(rh, "mask_head", None)
 
         def run_mask(sim=None, roles=None):
@@ -651,16 +595,17 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
 
         # a10-a12 predictors + losses (+ gradients w.r.t. the Linear outputs)
         lin_sup = lin_weak_sup = None
-        if rs > 0 and rw > 0 and c.head_overlap and self.sup_predictor_on_head_stream and not getattr(bp, "finetune", False):
+        if rs > 0 and rw > 0 and c.head_overlap and not getattr(bp, "finetune", False):
             # box_head's features were produced on the head stream and its losses will run there: the supervised predictors' GEMM goes there
             # too, at once, instead of queueing behind the weak predictors' on this stream (two 16- / 32-workgroup launches of ~25 us each)
             with torch.cuda.stream(self._head_stream):
                 lin_sup = bp.group.fwd(c.box_feat)
-                if sup_rows_done is not None and self.decoupled_sup_chain and not torch.cuda.is_current_stream_capturing():
+                if sup_rows_done is not None and not torch.cuda.is_current_stream_capturing():
                     # (eager launches only: hipStreamEndCapture of ROCm 7.2 segfaults on the capture of this cross-stream event wait)
                     # three-chain form: the weak predictors' outputs on the SUPERVISED RoIs (the OICR columns that feed the supervised scores)
-                    # need the chain on the weight-gradient stream only -- with them computed here, the supervised losses and (early_sup_backward)
-                    # box_head's backward no longer wait for weak_box_head's pass over the weak RoIs on the main stream, the longest of the three
+                    # need the chain on the weight-gradient stream only -- with them computed here, the supervised losses and box_head's
+                    # backward (backward_train: `early_sup`) no longer wait for weak_box_head's pass over the weak RoIs on the main stream,
+                    # the longest of the three
                     self._head_stream.wait_event(sup_rows_done)
                     lin_weak_sup = bp.weak_detector_head.group.fwd(wfeat_all[:rs])
         decoupled = lin_weak_sup is not None
@@ -670,6 +615,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             lin_weak_all = bp.weak_detector_head.group.fwd(wfeat_all)            # [rs+rw, 104] (oicr cols feed the sup scores)
             lin_weak_sup, lin_weak_w = lin_weak_all[:rs], lin_weak_all[rs:]
         c.dy_sup = c.dy_weak = None
+        c.sup_losses_on_head_stream = False
         sup_side = None
         if rs > 0:
             if lin_sup is None:
@@ -760,7 +706,14 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             self._clear_unproduced(c)
 
         dbox = dweak = dall_buf = None
-        early_sup = False
+        # overlap: the two Res5 heads' backward as two chains, box_head's on the head stream. Requires that the forward ran them that way
+        # (c.head_overlap: two heads, streams on, no mask head), that box_head trains and that both RoI groups produced a gradient.
+        overlap = c.head_overlap and box_trainable and c.dy_sup is not None and c.dy_weak is not None
+        # early_sup: the supervised predictors' backward already runs on the head stream, behind the supervised losses that ran there beside
+        # the (three times longer) weak loss chain on this one, so box_head's backward starts ~0.3 ms before weak_box_head's, while only one-
+        # and two-workgroup loss kernels run (profiles/r04_exp_head_backward_start.txt). Requires `overlap`, the losses on the head stream
+        # (never in a fine-tune step) and eager launches (a captured segment must fork the head stream itself).
+        early_sup = overlap and c.sup_losses_on_head_stream and not torch.cuda.is_current_stream_capturing()
         if c.dy_sup is not None and getattr(bp, "finetune", False):
             # VOC fine-tune yaml: everything below the ft heads is frozen -> their weight gradients are all there is.
             # COCO segm fine-tune yaml: the box head (and RPN) train -> the gradient continues through the ft heads, the frozen
@@ -778,13 +731,6 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 dlin_w = similarity_backward(rh, c.lin_w_box, lingual, keys, dsim, dt)          # (one matrix for all heads: asserted there)
                 dbox = dbox + bp.group.bwd(c.box_feat, dlin, need_dx=True) + wh.group.bwd(c.box_feat, dlin_w, need_dx=True)
         elif c.dy_sup is not None:
-            # The supervised losses ran on the head stream, beside the (three times longer) weak loss chain on this one. With
-            # early_sup_backward the supervised predictor's backward and box_head's backward follow them THERE without waiting for this
-            # stream: box_head's backward starts ~0.3 ms before weak_box_head's, in the window where only one- and two-workgroup loss
-            # kernels run (profiles/r04_exp_head_backward_start.txt).
-            early_sup = (self.early_sup_backward and multi and c.head_overlap and box_trainable and c.dy_weak is not None
-                         and getattr(c, "sup_losses_on_head_stream", False) and getattr(c, "mask_ctx", None) is None
-                         and not torch.cuda.is_current_stream_capturing())      # (a captured segment must fork the head stream itself)
             if early_sup:
                 with torch.cuda.stream(self._head_stream):
                     dbox = bp.group.bwd(c.box_feat, c.dy_sup, need_dx=True)
@@ -803,7 +749,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         done("heads")
         dpool_sup = dpool_weak = None      # d(loss)/d(pooled) of the supervised / weak RoIs
         mask_hook = None
-        if getattr(c, "mask_ctx", None) is not None:
+        if c.mask_ctx is not None:
             mh = rh.mask_head
 
             def mask_hook(g, y):
@@ -816,7 +762,6 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                     mh.deconv.dgrad(dy1[i * fgc:(i + 1) * fgc], residual=g[sl], mask_ref=y[sl], out=g[sl])
                 done("mask_head")
         if multi:
-            overlap = c.head_overlap and dbox is not None and box_trainable and dweak is not None
             if overlap:
                 main, s1 = torch.cuda.current_stream(), self._head_stream
                 if not early_sup:
@@ -845,7 +790,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 dpool_sup, dpool_weak = (dpool[:rs] if rs > 0 else None), (dpool[rs:] if rw > 0 else None)
 
         drpn = None
-        if getattr(c, "rpn_bwd_early", False):
+        if c.rpn_bwd_early:
             torch.cuda.current_stream().wait_event(c.rpn_branch_done)      # launched during the forward plan
             if side is not None:
                 side.wait_event(c.rpn_branch_done)                         # its wgrad slabs are reduced on the side stream
@@ -870,7 +815,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                     ops.add_cast(ops.zeros(ft.shape, torch.float32, ft.device), add, dt, mask_ref=ft, out=out)
                 return out
 
-            if not getattr(c, "split", False):
+            if not c.split:
                 g = torch.empty_like(feat)
                 n_img, fh, fw, _ = feat.shape
                 for (dp, lo, hi, r_lo, r_hi, add) in ((dpool_sup, 0, n_sup, 0, rs, drpn), (dpool_weak, n_sup, n_img, rs, rs + rw, None)):
@@ -883,7 +828,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                         z = ops.zeros(feat[lo:hi].shape, torch.float32, feat.device)
                         ops.add_cast(z, add, dt, mask_ref=feat[lo:hi], out=g[lo:hi])
                 self.backbone.bwd(c.bb_ctx, g, on_stage_done=done)
-            elif getattr(c, "ragged", False):
+            elif c.ragged:
                 # ragged batches, single pass: the two groups' gradient maps are the rows of ONE ops.Ragged; one backward pass
                 gr = ops.Ragged.empty([tuple(feat.shape[:3]), tuple(c.feat_w.shape[:3])], feat.shape[3], feat)
                 grad_map(feat, dpool_sup, n_sup, 0, rs, 0, drpn, out=gr.group(0))
@@ -998,11 +943,11 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             return False   # (without the plan the wgrad kernels share one workspace and must stay on one stream)
         if getattr(self, "_head_stream", None) is None:
             # UNIT_STREAM_MERGE (experiment switch): which of the three side roles share ONE stream object -- "hw" head + weight gradients,
-            # "hr" head + RPN branch, "wr" weight gradients + RPN branch, "all" one side stream; "" = three streams (which of them share a
-            # HARDWARE queue is then the runtime's choice: GPU_MAX_HW_QUEUES = 4 queues for five streams)
+            # "hr" head + RPN branch, "wr" weight gradients + RPN branch, "all" one side stream; "" (default) = three streams placed by a probe
+            # on three hardware queues of their own (profiles/r04_exp_stream_queues.txt)
             merge = os.environ.get("UNIT_STREAM_MERGE", "")
-            if merge == "" and os.environ.get("UNIT_STREAM_PROBE", "1") != "0" and not torch.cuda.is_current_stream_capturing():
-                # three side streams on three hardware queues of their own (measured, not assumed: ops.streams_on_distinct_queues)
+            if merge == "" and not torch.cuda.is_current_stream_capturing():
+                # (measured, not assumed: ops.streams_on_distinct_queues; under capture the probe cannot run: the streams PyTorch hands out)
                 self._head_stream, self._wgrad_stream, self._rpn_stream = ops.streams_on_distinct_queues(self.device, 3)
                 return True
             self._head_stream = torch.cuda.Stream(self.device)

@@ -182,7 +182,6 @@ def stream_wait_stream(waiter, signaller_raw=None):
 _WS = {}
 
 
-
 def _big_tile_default(dtype, m, k, c, kgemm):
     """use the 256x256 LDS-DMA kernel when it pays (measured, tools/microbench.py): bf16, C % 64 == 0, at least half a
     round of 256x256 tiles and a k-extent long enough to amortise the 128 KB-per-tile epilogue"""
@@ -525,9 +524,6 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
 
 
 FUSE_EPILOGUE = os.environ.get("UNIT_FUSE_EPILOGUE", "1") != "0"          # Res5 heads: average pool + ReLU bit mask inside the last conv's epilogue (conv2d_ex); False = separate kernels
-
-
-FUSE_DUAL = os.environ.get("UNIT_FUSE_DUAL", "1") != "0"          # first Res5 block: conv3 + shortcut (and their dgrads) as dual-input GEMMs
 
 
 def conv_ex_supported(dtype, c, ldy):
