@@ -1,8 +1,9 @@
-"""How unit_conv2d_wgrad_group deals the units of a grouped weight-gradient grid to the XCDs (csrc/conv_wgrad.hip), checked without a GPU
+"""How unit_conv2d_wgrad_group deals the units of a grouped weight-gradient grid to the XCDs (csrc/conv_wgrad_plan.hip), checked without a GPU
 through unit_conv2d_wgrad_group_layout: every tile of every (layer [, filter tap], split) exactly once, the slots of an XCD gap-free, the units
 that contract over the same rows on ONE XCD (profiles/r06_exp_wgrad_gangs.txt), no rounds lost to the gangs."""
 import collections
 import ctypes
+import importlib.util
 import os
 
 import pytest
@@ -12,35 +13,15 @@ from unit_amd import _lib, ops
 BF16 = ops.BF16
 
 
-def layers_of(which):
-    L = []
-    if which == "res5":       # one Res5 head on 1024 RoIs: block 0 (stride 2 from 14x14) + 2 identity blocks
-        n = 1024
-        L += [(n, 14, 14, 1024, 512, 1, 2, 0), (n, 7, 7, 512, 512, 3, 1, 1), (n, 7, 7, 512, 2048, 1, 1, 0), (n, 14, 14, 1024, 2048, 1, 2, 0)]
-        for _ in range(2):
-            L += [(n, 7, 7, 2048, 512, 1, 1, 0), (n, 7, 7, 512, 512, 3, 1, 1), (n, 7, 7, 512, 2048, 1, 1, 0)]
-    elif which == "res4":     # a six-block gradient bucket of res4 on four 600x1000 images
-        for _ in range(6):
-            L += [(4, 38, 63, 1024, 256, 1, 1, 0), (4, 38, 63, 256, 256, 3, 1, 1), (4, 38, 63, 256, 1024, 1, 1, 0)]
-    elif which == "long":     # more layers than one launch holds (WG_GROUP_MAX_PROBLEMS = 20)
-        for _ in range(9):
-            L += [(4, 38, 63, 1024, 256, 1, 1, 0), (4, 38, 63, 256, 256, 3, 1, 1), (4, 38, 63, 256, 1024, 1, 1, 0)]
-    else:                     # res3: 128-wide tiles, and one 256 -> 512 shortcut that joins them
-        L += [(4, 150, 250, 256, 128, 1, 2, 0), (4, 75, 125, 128, 128, 3, 1, 1), (4, 75, 125, 128, 512, 1, 1, 0), (4, 150, 250, 256, 512, 1, 2, 0)]
-        for _ in range(3):
-            L += [(4, 75, 125, 512, 128, 1, 1, 0), (4, 75, 125, 128, 128, 3, 1, 1), (4, 75, 125, 128, 512, 1, 1, 0)]
-    return L
+def _lists():
+    """the problem lists live with the generator of the parent fixture (tests/golden/gen_wgrad_layout_parent.py): one definition for both"""
+    spec = importlib.util.spec_from_file_location("gen_wgrad_layout_parent", os.path.join(os.path.dirname(__file__), "golden", "gen_wgrad_layout_parent.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
-def planned(which, hint=0):
-    L = layers_of(which)
-    pr = (ops.WgradProblem * len(L))()
-    for q, (n, h, w, c, k, r, stride, pad) in zip(pr, L):
-        oh, ow = ops.conv_out_size(h, w, r, r, stride, pad)
-        q.x, q.dy, q.partial = 0x10000, 0x20000, 0x30000          # aligned, never read by the layout call
-        q.N, q.H, q.W, q.C, q.K, q.R, q.S, q.stride, q.pad, q.OH, q.OW, q.ldy = n, h, w, c, k, r, r, stride, pad, oh, ow, k
-    assert _lib.lib().unit_conv2d_wgrad_group_plan(pr, len(L), hint) == 0
-    return pr
+planned = _lists().planned          # planned(which, hint=0) -> the planned ctypes problem array
 
 
 def layout(pr):
@@ -72,7 +53,8 @@ def gang_mode():
     set_mode(old)
 
 
-@pytest.mark.parametrize("which,hint", [("res5", 0), ("res5", 4), ("res4", 0), ("res4", 3), ("res3", 0), ("long", 0)])
+@pytest.mark.parametrize("which,hint", [("res5", 0), ("res5", 4), ("res4", 0), ("res4", 3), ("res3", 0), ("long", 0), ("chunk2", 0), ("chunk1", 0),
+                                        ("full", 0), ("full2", 0), ("tight", 0)])
 @pytest.mark.parametrize("mode", [None, 0, 1, 2])
 def test_every_tile_once_and_slots_gap_free(which, hint, mode, gang_mode):
     gang_mode(mode)

@@ -170,7 +170,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad128_ring_kernel(Wgrad256Args
 // 5-11 GFLOP, 100 launches per step). The layers of a gradient bucket (18 of them for six res4 blocks) have 408 tiles between them:
 // one grid, ONE slab per layer, 150-step loops. A "unit" = (layer, split): its tiles read the same pixel rows, so a unit is dealt
 // to ONE XCD (workgroup b runs on XCD b % 8) and its rows come through that XCD's L2 once; the host deals units to XCDs
-// longest-first (conv_wgrad.hip).
+// longest-first (conv_wgrad_plan.hip).
 __device__ __forceinline__ int pin(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ const void* pin_ptr(const void* q) {
   unsigned long long u = (unsigned long long)(uintptr_t)q;
@@ -182,12 +182,12 @@ template <int NS>
 __global__ void __launch_bounds__(256, 2) conv_wgrad128_group_kernel(WgradGroupArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  int nu = g.n_units[xcd];
-  if (slot >= (int)g.unit_start[xcd][nu]) return;
+  int nu = g.t.n_units[xcd];
+  if (slot >= (int)g.t.unit_start[xcd][nu]) return;
   int u = 0;
   for (int i = 1; i < nu; ++i)
-    if (slot >= (int)g.unit_start[xcd][i]) u = i;
-  unsigned code = g.unit_code[xcd][u];
+    if (slot >= (int)g.t.unit_start[xcd][i]) u = i;
+  unsigned code = g.t.unit_code[xcd][u];
   // the layer's arguments into SGPRs ONCE: read in place, hipcc re-loads fields from the argument segment inside the pixel loop, and
   // every such s_load is followed by an lgkmcnt(0) wait that also drains the LDS reads in flight
   const Wgrad256Args& src = g.p[code & 31];
@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(256, 2) conv_wgrad128_group_kernel(WgradGroupA
   p.m_per_split = pin(src.m_per_split); p.x_bytes = (unsigned)pin((int)src.x_bytes); p.dy_bytes = (unsigned)pin((int)src.dy_bytes);
   p.magic_ohw = (unsigned)pin((int)src.magic_ohw); p.magic_ow = (unsigned)pin((int)src.magic_ow); p.OHW = pin(src.OHW);
   p.use_magic = pin(src.use_magic); p.valid_only = 0; p.x_pitch = pin(src.x_pitch);
-  int t = slot - (int)g.unit_start[xcd][u] + (int)g.unit_tile0[xcd][u];
+  int t = slot - (int)g.t.unit_start[xcd][u] + (int)g.t.unit_tile0[xcd][u];
   wgrad128_ring_tile<NS>(p, t % p.tiles_k, t / p.tiles_k, (int)(code >> 9), smem);
 }
 

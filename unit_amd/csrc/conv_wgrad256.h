@@ -34,15 +34,25 @@ struct Wgrad256Args {
 constexpr int WG_GROUP_MAX_PROBLEMS = 20;
 constexpr int WG_GROUP_MAX_UNITS = 24;           // per XCD
 constexpr int WG_GROUP_MAX_SPLITS = 127;
-struct WgradGroupArgs {
-  Wgrad256Args p[WG_GROUP_MAX_PROBLEMS];
+struct WgradUnitTable {
   unsigned short unit_start[8][WG_GROUP_MAX_UNITS + 1];   // per XCD: first workgroup slot of unit i ([n_units] = the XCD's total)
-  unsigned short unit_code[8][WG_GROUP_MAX_UNITS];        // problem (5 bits) | filter tap << 5 (4 bits) | split << 9
+  unsigned short unit_code[8][WG_GROUP_MAX_UNITS];        // pack_unit_code: problem (5 bits) | filter tap << 5 (4 bits) | split << 9
   unsigned short unit_tile0[8][WG_GROUP_MAX_UNITS];       // first tile of the unit within its (layer [, tap], split): layers with more
                                                           // tiles than an XCD has workgroup slots are cut into several units
   int n_units[8];
 };
+// the host's side of unit_code (the kernels decode with their own shifts)
+static_assert(WG_GROUP_MAX_PROBLEMS <= 32 && 9 <= 16 && WG_GROUP_MAX_SPLITS < 128, "unit code: 5 bits of problem, 4 of tap, 7 of split");
+struct WgradUnitCode { int problem, tap, split; };
+inline unsigned short pack_unit_code(int problem, int tap, int split) { return (unsigned short)(problem | (tap << 5) | (split << 9)); }
+inline WgradUnitCode unpack_unit_code(unsigned code) { return WgradUnitCode{(int)(code & 31), (int)((code >> 5) & 15), (int)(code >> 9)}; }
+
+struct WgradGroupArgs {
+  Wgrad256Args p[WG_GROUP_MAX_PROBLEMS];
+  WgradUnitTable t;
+};
 static_assert(sizeof(WgradGroupArgs) <= 4000, "kernel-argument segment is 4 KB");
+static_assert(sizeof(WgradGroupArgs) == 3760 && offsetof(WgradGroupArgs, t) == 2560, "the by-value kernel argument keeps its byte layout");
 int unit_wgrad128_group_launch(const WgradGroupArgs& g, int slots_per_xcd, hipStream_t st);
 int unit_wgrad256_group_launch(const WgradGroupArgs& g, int slots_per_xcd, hipStream_t st);
 

@@ -152,40 +152,7 @@ __global__ void __launch_bounds__(512, 2) conv_wgrad256_kernel(Wgrad256Args p) {
 // removed) and the interleaved schedules measured SLOWER than the two-stage loop. With the wait gone (tools/wgrad_bench.py):
 // 512->2048: two-stage 139 -> 121 us, ring 115, interleaved 113; 2048->512: 139 -> 126 / 112 / 103 us.
 
-// shared with conv_wgrad.hip: which kernel handles a shape, and with how many split-M slabs
-extern "C" int unit_wgrad_use_big(int in_dtype, long M, int K, int C, int RS) {
-  if (in_dtype != UNIT_BF16 || (C % 256) != 0 || (K % 256) != 0) return 0;
-  // few pixels need many tiles: with >= 96 tiles (RPN 3x3 1024->1024 on 4 images: 144) two or three split-M slabs fill the chip
-  // and each workgroup still runs >= 50 steps; the backbone layers (4-16 tiles) would need ~64 slabs of 2-3 steps each
-  long tiles = (long)(RS * C / 256) * (K / 256);
-  return M >= 16384 || (M >= 8192 && tiles >= 96);
-}
-
-// 3x3 convs on small maps get one spare slab: the valid-only contraction of conv_wgrad256p8.hip deals its workgroups to the filter
-// taps unevenly (Wgrad256Args::valid_only); where that path does not apply the spare is simply one more split
-extern "C" int unit_wgrad_big_splits_base(long M, int tiles);
-extern "C" int unit_wgrad_big_splits(long M, int tiles, int R, int S, int OHW) {
-  int s = unit_wgrad_big_splits_base(M, tiles);
-  return (R == 3 && S == 3 && OHW <= 512) ? s + 1 : s;
-}
-
-extern "C" int unit_wgrad_big_splits_base(long M, int tiles) {
-  // one workgroup per CU (128 KB of LDS): 256 slots per round; >= 8 staged steps per split. Cost model (us): a workgroup
-  // needs ~6 us of fixed time plus ~1.3 us per 64-pixel step; the grid runs in rounds of 256 workgroups; every workgroup
-  // writes a 256 KB fp32 slab that the reduction reads back (~2 x 256 KB at ~4 TB/s).
-  int maxs = (int)((M + 8 * 64 - 1) / (8 * 64));
-  if (maxs < 1) maxs = 1;
-  if (maxs > 64) maxs = 64;
-  int best = 1; double best_cost = 1e30;
-  double steps_total = (double)((M + 63) / 64);
-  for (int s = 1; s <= maxs; ++s) {
-    long blocks = (long)tiles * s;
-    long rounds = (blocks + 255) / 256;
-    double cost = rounds * (6.0 + 1.3 * steps_total / s) + (double)blocks * 2.0 * 262144.0 / 4.0e6;
-    if (cost < best_cost) { best_cost = cost; best = s; }
-  }
-  return best;
-}
+// (which shapes this tile handles, and with how many split-M slabs: conv_wgrad_plan.hip)
 
 // launches the 256x256 tile on a filled argument block; returns the number of slabs written or a negative status
 int unit_wgrad_big_launch_args(Wgrad256Args& a, int variant, size_t workspace_bytes, hipStream_t st) {
@@ -196,7 +163,7 @@ int unit_wgrad_big_launch_args(Wgrad256Args& a, int variant, size_t workspace_by
   if (variant == 0) {
     variant = ((a.R == 1 && a.S == 1 && a.stride == 1 && a.pad == 0) || a.OHW <= 1024) ? 3 : 2;
     // 3x3 s1 p1 "same" conv on a small map: contract only over the pixels whose tap lies inside the map (Wgrad256Args::valid_only)
-    if (variant == 3 && a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W && a.OHW <= 512) a.valid_only = 1;
+    if (variant == 3 && wgrad_valid_only(a)) a.valid_only = 1;
   }
   if (variant == 3) {
     int rc = unit_wgrad256_p8_launch(a, st);

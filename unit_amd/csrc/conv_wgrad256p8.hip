@@ -612,7 +612,7 @@ __global__ void __launch_bounds__(512, 2) conv_wgrad256_p8_kernel(Wgrad256Args p
 }
 
 // which loop schedule a launch runs (the template parameter SCHED of the tile): UNIT_WGRAD_LOOP, read per launch like UNIT_WGRAD_GANG
-// (conv_wgrad.hip) so that the tests and A/B runs switch it in-process. Every schedule writes the same slabs bit for bit.
+// (conv_wgrad_plan.hip) so that the tests and A/B runs switch it in-process. Every schedule writes the same slabs bit for bit.
 static int wgrad256_loop_sched() {
   const char* e = getenv("UNIT_WGRAD_LOOP");
   int v = e && *e ? atoi(e) : W8_DEFAULT_SCHED;
@@ -643,7 +643,7 @@ int unit_wgrad256_p8_launch(const Wgrad256Args& a, hipStream_t st) {
 
 // ---- grouped launch (include/unit_hip.h: unit_conv2d_wgrad_group): the 256x256 tiles of SEVERAL layers in one grid. A unit = the tiles of
 // one (layer, split) -- for valid_only layers of one (layer, filter tap, split): they contract over the same rows -- dealt to ONE XCD by
-// the host (conv_wgrad.hip), longest first. With the layers of a Res5 head in one grid every layer needs 3-4 split-M slabs instead of
+// the host (conv_wgrad_plan.hip), longest first. With the layers of a Res5 head in one grid every layer needs 3-4 split-M slabs instead of
 // 8-16 (launched alone, 16 tiles have to become 256 workgroups): a quarter of the slab traffic, 200-step loops; the res4 layers of a
 // gradient bucket get 256x256 tiles at all (half the operand bytes per flop of the 128x128 ring kernel).
 __device__ __forceinline__ int pinw(int v) { return __builtin_amdgcn_readfirstlane(v); }
@@ -657,12 +657,12 @@ template <int SCHED>
 __global__ void __launch_bounds__(512, 2) conv_wgrad256_group_kernel(WgradGroupArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  int nu = g.n_units[xcd];
-  if (slot >= (int)g.unit_start[xcd][nu]) return;
+  int nu = g.t.n_units[xcd];
+  if (slot >= (int)g.t.unit_start[xcd][nu]) return;
   int u = 0;
   for (int i = 1; i < nu; ++i)
-    if (slot >= (int)g.unit_start[xcd][i]) u = i;
-  unsigned code = g.unit_code[xcd][u];
+    if (slot >= (int)g.t.unit_start[xcd][i]) u = i;
+  unsigned code = g.t.unit_code[xcd][u];
   const Wgrad256Args& src = g.p[code & 31];     // into SGPRs once (conv_wgrad128r.hip)
   Wgrad256Args p;
   p.x = pinw_ptr(src.x); p.dy = pinw_ptr(src.dy); p.partial = (float*)pinw_ptr(src.partial);
@@ -672,7 +672,7 @@ __global__ void __launch_bounds__(512, 2) conv_wgrad256_group_kernel(WgradGroupA
   p.m_per_split = pinw(src.m_per_split); p.x_bytes = (unsigned)pinw((int)src.x_bytes); p.dy_bytes = (unsigned)pinw((int)src.dy_bytes);
   p.magic_ohw = (unsigned)pinw((int)src.magic_ohw); p.magic_ow = (unsigned)pinw((int)src.magic_ow); p.OHW = pinw(src.OHW);
   p.use_magic = pinw(src.use_magic); p.valid_only = pinw(src.valid_only); p.x_pitch = pinw(src.x_pitch);
-  int t = slot - (int)g.unit_start[xcd][u] + (int)g.unit_tile0[xcd][u];
+  int t = slot - (int)g.t.unit_start[xcd][u] + (int)g.t.unit_tile0[xcd][u];
   int tap = (int)((code >> 5) & 15), split = (int)(code >> 9);
   if (p.valid_only) {
     int ncb = p.tiles_k / (p.R * p.S);

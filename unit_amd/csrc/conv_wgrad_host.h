@@ -1,11 +1,13 @@
 // conv_wgrad_host.h -- host side of every weight-gradient launch: THE per-layer decision (kernel family, staging step, split-M slabs:
-// wgrad_select) and THE fill of the kernels' argument block (wgrad_fill). Nothing in here launches, so the file also compiles into a
-// host-only program. A new field of Wgrad256Args is derived in wgrad_fill and nowhere else; a new rule of the decision goes into
-// wgrad_select, which is what the workspace / split queries and the launches all ask.
+// wgrad_select), THE fill of the kernels' argument block (wgrad_fill) and what the planner of the grouped launches (conv_wgrad_plan.hip)
+// exposes to the file that launches them (conv_wgrad.hip). Nothing in here launches and every extern below is defined in
+// conv_wgrad_plan.hip, which holds no kernel: a host-only program links against that one file (tools/wgrad_plan_check.hip does, under
+// sanitizers). A new field of Wgrad256Args is derived in wgrad_fill and nowhere else; a new rule of the decision goes into wgrad_select,
+// which is what the workspace / split queries and the launches all ask.
 #pragma once
 #include "conv_wgrad256.h"
 
-// conv_wgrad256.hip: does the 256x256 tile handle a shape, and with how many split-M slabs
+// does the 256x256 tile handle a shape, and with how many split-M slabs
 extern "C" int unit_wgrad_use_big(int in_dtype, long M, int K, int C, int RS);
 extern "C" int unit_wgrad_big_splits(long M, int tiles, int R, int S, int OHW);
 
@@ -78,3 +80,26 @@ inline int wgrad_fill(Wgrad256Args& a, const char* too_large, const void* x, con
   a.valid_only = 0;
   return UNIT_OK;
 }
+
+// THE rule for "contract over in-map pixels only" (Wgrad256Args::valid_only): a 3x3 s1 p1 "same" conv on a small map. Asked by the 256
+// tile's policy (conv_wgrad256.hip) and by the grouped launches' fill; the grouped launches' units follow the flag.
+inline bool wgrad_valid_only(const Wgrad256Args& a) {
+  return a.R == 3 && a.S == 3 && a.stride == 1 && a.pad == 1 && a.OH == a.H && a.OW == a.W && a.OHW <= 512;
+}
+
+// ---- grouped launches: the planner (conv_wgrad_plan.hip) ------------------------------------------------------------------------------
+// mirrors include/unit_hip.h
+struct UnitWgradProblem {
+  const void* x; const void* dy; void* partial;
+  int N, H, W, C, K, R, S, stride, pad, OH, OW, ldy;
+  int splits, kind;
+  int x_pitch;            // 0 = C; one pass of a bf16x3 weight gradient: 2 * C (x, dy point at the pass's planes, ldy = 2 * K), x_back / dy_back =
+  int x_back, dy_back;    // elements between the tensor's start and the x / dy pointer (0 or one plane: keeps the loads' buffer range exact)
+};
+
+// every launch of the problems' grids in order -- the 256-tile kind first, per kind as many launches as WG_GROUP_MAX_PROBLEMS and the unit
+// table need: `each` gets the filled kernel argument (layer blocks + unit table), the tile kind, the workgroup slots of the fullest XCD
+// (grid = 8 x that) and, per layer block, its index into pr. Stops at the first status != UNIT_OK and returns it. Reads the dealing
+// switches (UNIT_WGRAD_GANG / UNIT_WGRAD_DEAL) once per call.
+typedef int (*WgradLaunchFn)(void* ctx, const WgradGroupArgs& g, int kind, int slots_per_xcd, const int* pidx);
+int wgrad_group_each_launch(const UnitWgradProblem* pr, int n, WgradLaunchFn each, void* ctx);
