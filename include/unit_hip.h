@@ -450,6 +450,18 @@ int unit_transfer_predictions(const float* lin, int ld, int ccol0, int bcol0, in
                               const float* ft, int ldf, int fccol0, int fbcol0, const float* sim_cls, const float* sim_bbox,
                               const int* base_dev, int n_base, const int* novel_dev, int n_novel, const int8_t* role_dev,
                               const int* slot_dev, float* scores, int lds, float* bbox, int ldb, int R, void* stream);
+/* unit_transfer_predictions with WEAK_DETECTOR.REGRESSION_BRANCH under the fine-tune predictor (fast_rcnn.py:484-533 with :360-364 and
+ * :370-374): wbcol0 is the first column, inside `weak`, of the [R, 4K] block regression_branch_bbox(x_weak); -1 for none. One launch writes
+ *   scores = ((delta + transfer(delta)) + mean of n_oicr blocks of weak at wcol0) + ft        (:504-512, :525, :527; the caller passes
+ *                                                                                               wcol0 = regression_branch_cls, n_oicr = 1)
+ *   bbox   = ((base: delta | novel: sim . delta_base | else 0) + weak[r, wbcol0 + 4c + j]) + ft (:514-523, :526, :528)
+ * in that order of fp32 additions. wbcol0 >= 0 needs weak != NULL and wbcol0 + 4K <= ldw; n_base <= 96; R == 0 launches nothing. With
+ * wbcol0 = -1 the outputs are unit_transfer_predictions' bit for bit. The weak terms carry no gradient (evaluated under no_grad, :490-494):
+ * unit_transfer_predictions_bwd serves both. */
+int unit_transfer_predictions_ex(const float* lin, int ld, int ccol0, int bcol0, int K, const float* weak, int ldw, int wcol0, int n_oicr,
+                                 int wbcol0, const float* ft, int ldf, int fccol0, int fbcol0, const float* sim_cls, const float* sim_bbox,
+                                 const int* base_dev, int n_base, const int* novel_dev, int n_novel, const int8_t* role_dev,
+                                 const int* slot_dev, float* scores, int lds, float* bbox, int ldb, int R, void* stream);
 /* backward of the two above for the fine-tune configurations whose box head trains (COCO-RCNN-50-C4-split1-segm-ft.yaml; the reference
  * computes the similarity with grad in training, roi_heads.py:852): dy = d(loss)/d[scores | bbox] in the ft heads' layout ->
  * dlin (delta heads' layout, zero-filled first) and dsim [R][n_novel][n_base] (written); then dsim -> the OICR logit columns of dlin_weak */

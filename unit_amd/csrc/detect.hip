@@ -95,8 +95,13 @@ extern "C" int unit_similarity(const float* lin_weak, int ld, int col0, int n_oi
 // fast_rcnn.py:401-423 / 504-523 + :425-426 (+ :525-528 fine-tune heads):
 //   scores[r,c] = delta[r,c] + [c novel] sum_b sim_cls[r,j,b] * delta[r,base_b]  + mean_k oicr_k  (+ ft)
 //   bbox[r,c,:] = (c base) delta ; (c novel) sum_b sim_bbox[r,j,b] * delta[r,base_b,:] ; (else) 0   (+ 0 weak) (+ ft)
+// WB (unit_transfer_predictions_ex, REGRESSION_BRANCH under the fine-tune predictor): the [R, 4K] block of weak box deltas at column wbcol0 of
+// `weak` is added BEFORE the ft term, (o + weak) + ft -- get_cls_bbox (fast_rcnn.py:370-374, :526) runs before `bbox + proposal_ft` (:528).
+// Latency-sized (R * (K + 1) threads, a few hundred rows): the base-class loop reads its row of `lin` through L1 / L2 as before; staging the
+// row in LDS would add a barrier to a launch whose time is the launch.
+template <bool WB>
 __global__ void transfer_kernel(const float* __restrict__ lin, int ld, int ccol0, int bcol0, int K, const float* __restrict__ weak, int ldw,
-                                int wcol0, int n_oicr, const float* __restrict__ ft, int ldf, int fccol0, int fbcol0,
+                                int wcol0, int n_oicr, int wbcol0, const float* __restrict__ ft, int ldf, int fccol0, int fbcol0,
                                 const float* __restrict__ sim_cls, const float* __restrict__ sim_bbox, const int* __restrict__ base, int n_base,
                                 const int* __restrict__ novel, int n_novel, const int8_t* __restrict__ role /* K: 0 none,1 base,2 novel */,
                                 const int* __restrict__ slot /* K: index into base/novel list */, float* __restrict__ scores, int lds_,
@@ -133,6 +138,10 @@ __global__ void transfer_kernel(const float* __restrict__ lin, int ld, int ccol0
       for (int j = 0; j < 4; ++j) o[j] += w * x[bcol0 + 4 * base[b] + j];
     }
   }
+  if (WB) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = o[j] + weak[(size_t)r * ldw + wbcol0 + 4 * c + j];
+  }
 #pragma unroll
   for (int j = 0; j < 4; ++j) bbox[(size_t)r * ldb + 4 * c + j] = o[j] + (ft ? ft[(size_t)r * ldf + fbcol0 + 4 * c + j] : 0.f);
 }
@@ -142,9 +151,31 @@ extern "C" int unit_transfer_predictions(const float* lin, int ld, int ccol0, in
                                          const int8_t* role_dev, const int* slot_dev, float* scores, int lds, float* bbox, int ldb,
                                          int R, void* stream) {
   if (R == 0) return UNIT_OK;
-  transfer_kernel<<<cdiv(R * (K + 1), 256), 256, 0, (hipStream_t)stream>>>(lin, ld, ccol0, bcol0, K, weak, ldw, wcol0, n_oicr, ft, ldf, fccol0,
-                                                                       fbcol0, sim_cls, sim_bbox, base_dev, n_base, novel_dev, n_novel,
-                                                                       role_dev, slot_dev, scores, lds, bbox, ldb, R);
+  transfer_kernel<false><<<cdiv(R * (K + 1), 256), 256, 0, (hipStream_t)stream>>>(lin, ld, ccol0, bcol0, K, weak, ldw, wcol0, n_oicr, -1, ft, ldf,
+                                                                              fccol0, fbcol0, sim_cls, sim_bbox, base_dev, n_base, novel_dev,
+                                                                              n_novel, role_dev, slot_dev, scores, lds, bbox, ldb, R);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+// unit_transfer_predictions plus the weak head's box deltas: wbcol0 >= 0 is the first of 4K columns of `weak` added to the transferred deltas
+// before the ft term; wbcol0 < 0 is the entry above, bit for bit (the same instantiation).
+extern "C" int unit_transfer_predictions_ex(const float* lin, int ld, int ccol0, int bcol0, int K, const float* weak, int ldw, int wcol0,
+                                            int n_oicr, int wbcol0, const float* ft, int ldf, int fccol0, int fbcol0, const float* sim_cls,
+                                            const float* sim_bbox, const int* base_dev, int n_base, const int* novel_dev, int n_novel,
+                                            const int8_t* role_dev, const int* slot_dev, float* scores, int lds, float* bbox, int ldb,
+                                            int R, void* stream) {
+  if (R == 0) return UNIT_OK;          // (an empty matrix has no address: nothing to check, nothing to launch)
+  UNIT_CHECK_ARG(wbcol0 < 0 || weak != nullptr, "transfer_predictions_ex: wbcol0 names columns of `weak`, which is NULL");
+  UNIT_CHECK_ARG(wbcol0 < 0 || (long)wbcol0 + 4L * K <= (long)ldw, "transfer_predictions_ex: wbcol0 + 4K columns pass the row stride of `weak`");
+  UNIT_CHECK_ARG(n_base <= DET_MAXC, "transfer_predictions_ex: more than 96 base classes");
+  dim3 grid(cdiv(R * (K + 1), 256));
+  hipStream_t st = (hipStream_t)stream;
+  if (wbcol0 >= 0)
+    transfer_kernel<true><<<grid, 256, 0, st>>>(lin, ld, ccol0, bcol0, K, weak, ldw, wcol0, n_oicr, wbcol0, ft, ldf, fccol0, fbcol0, sim_cls, sim_bbox,
+                                                base_dev, n_base, novel_dev, n_novel, role_dev, slot_dev, scores, lds, bbox, ldb, R);
+  else
+    transfer_kernel<false><<<grid, 256, 0, st>>>(lin, ld, ccol0, bcol0, K, weak, ldw, wcol0, n_oicr, -1, ft, ldf, fccol0, fbcol0, sim_cls, sim_bbox,
+                                                 base_dev, n_base, novel_dev, n_novel, role_dev, slot_dev, scores, lds, bbox, ldb, R);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

@@ -358,9 +358,6 @@ class SupervisedDetectorOutputsBase(nn.Module):
         self.cls_score_delta = Linear(self.input_size, k + 1)
         self.bbox_pred_delta = Linear(self.input_size, k * 4)
         self.regression_branch = self.weak_detector_head.regression_branch
-        assert not (self.finetune and self.regression_branch), \
-            ("SupervisedDetectorOutputsFineTune with WEAK_DETECTOR.REGRESSION_BRANCH is not supported: the fine-tune stage on top of the weak "
-             "regression branch is not built (DESIGN.md section 8); SupervisedDetectorOutputsBase is")
         nn.init.constant_(self.cls_score_delta.weight, 0.)       # fast_rcnn.py:319
         if self.regression_branch:
             nn.init.constant_(self.bbox_pred_delta.weight, 0.)   # :322-323: the weak branch's deltas are the starting point
@@ -420,6 +417,24 @@ class SupervisedDetectorOutputsBase(nn.Module):
         if not self.regression_branch:
             return bbox
         return ops.sup_scores(bbox, col0, lin_weak, self.weak_detector_head.col_reg_bbox, 1, 4 * self.num_classes)
+
+    @property
+    def weak_bbox_col(self):
+        """FineTune with REGRESSION_BRANCH: the column of the weak head's box deltas that unit_transfer_predictions_ex adds in its one launch,
+        (o + weak) + ft as fast_rcnn.py:526, 528 sums them. None everywhere else: Base with the switch keeps unit_transfer_predictions followed
+        by add_weak_deltas, and no other configuration has weak deltas."""
+        return self.weak_detector_head.col_reg_bbox if (self.finetune and self.regression_branch) else None
+
+    def transfer(self, lin_sup, lin_weak, sim_cls, sim_bbox, t, ft=None):
+        """fast_rcnn.py:401-426 (Base, eval) / :504-528 (FineTune) -> (scores [R, K+1], bbox [R, 4K]) from the Linear outputs: the base -> novel
+        transfer, the weak head's scores (and, under REGRESSION_BRANCH, its box deltas) and the ft heads, in the reference's order of additions."""
+        wb = self.weak_bbox_col
+        scores, bbox = ops.transfer_predictions(lin_sup, self.col_cls, self.col_bbox, self.num_classes, lin_weak, *self.weak_detector_head.score_cols,
+                                                sim_cls, sim_bbox, t["base"], t["novel"], t["role"], t["slot"], ft=ft, fccol0=self.col_cls,
+                                                fbcol0=self.col_bbox, wbcol0=wb)
+        if wb is None:
+            bbox = self.add_weak_deltas(bbox, 0, lin_weak)          # Base: after the base -> novel transfer of the supervised deltas (:414-426)
+        return scores, bbox
 
 
     # ---- plugin surface: the reference's signatures (fast_rcnn.py:384,435,455). Forward values only (see WeakDetectorOutputsBase).
@@ -481,11 +496,7 @@ class SupervisedDetectorOutputsBase(nn.Module):
                     sm = sm[None].expand(r, -1, -1)
                 sims.append(sm.float().contiguous() if sm is not None else None)
             ft = self.group_ft.fwd(xc) if self.finetune else None
-            wcol, wn = wh.score_cols
-            scores, bbox = ops.transfer_predictions(lin_sup, self.col_cls, self.col_bbox, k, lin_w, wcol, wn, sims[0],
-                                                    sims[1], t["base"], t["novel"], t["role"], t["slot"], ft=ft, fccol0=self.col_cls,
-                                                    fbcol0=self.col_bbox)
-            bbox = self.add_weak_deltas(bbox, 0, lin_w)          # after the base -> novel transfer of the supervised deltas (:414-426)
+            scores, bbox = self.transfer(lin_sup, lin_w, sims[0], sims[1], t, ft=ft)
         else:
             wcol, wn = wh.score_cols
             scores = ops.sup_scores(lin_sup, self.col_cls, lin_w, wcol, wn, k + 1, t["novel_mask"] if self.training else None)
@@ -542,7 +553,8 @@ class SupervisedDetectorOutputsFineTune(SupervisedDetectorOutputsBase):
     finetune = True
 
     # ---- a14: SupervisedDetectorOutputsFineTune.forward fast_rcnn.py:484-533 (scores/bbox assembled by
-    # unit_transfer_predictions incl. the zero-initialised *_ft heads; no -inf fill) + FastRCNNOutputs.losses
+    # unit_transfer_predictions incl. the zero-initialised *_ft heads -- under REGRESSION_BRANCH by unit_transfer_predictions_ex, which adds the
+    # weak head's box deltas in the same launch: `transfer` above; no -inf fill) + FastRCNNOutputs.losses
     def ft_losses(self, scores, bbox, roi_cls, rois5, roi_gt, loss_out, grad_dtype):
         """d(loss)/d(scores|bbox) == d(loss)/d([cls_score_ft | bbox_pred_ft] outputs): the ft heads enter additively."""
         k = self.num_classes

@@ -118,10 +118,8 @@ def roi_heads_inference(rh, feat, props, pcount, hw, dt, with_mask=True, want_si
     sims = similarity_dict(rh, lin_w_box)
     t = class_roles(rh)
     ft = bp.group_ft.fwd(box_feat) if getattr(bp, "finetune", False) else None
-    scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_w_sup, *wh.score_cols,
-                                            sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"], ft=ft,
-                                            fccol0=bp.col_cls, fbcol0=bp.col_bbox)
-    bbox = bp.add_weak_deltas(bbox, 0, lin_w_sup)          # REGRESSION_BRANCH: + the weak deltas, after the transfer (fast_rcnn.py:414-426)
+    # REGRESSION_BRANCH: + the weak deltas after the transfer (fast_rcnn.py:414-426) -- Base: a second launch; FineTune: inside the one launch
+    scores, bbox = bp.transfer(lin_sup, lin_w_sup, sims["cls"], sims["bbox"], t, ft=ft)
     probs = ops.softmax_rows(scores, rh.num_classes + 1)
     boxes, sc, cls, roi, cnt = ops.detections(probs, bbox, props, pcount, hw, bp.bbox_reg_weights, bp.test_score_thresh,
                                               bp.test_nms_thresh, bp.test_topk_per_image)

@@ -630,9 +630,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                 c.lin_w_box = wh.group.fwd(c.box_feat)
                 sims, lingual, keys = similarity_dict(self, c.lin_w_box, want_ctx=True)
                 t = class_roles(self)
-                c.scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak_sup, *wh.score_cols,
-                                                          sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"],
-                                                          ft=lin_ft, fccol0=bp.col_cls, fbcol0=bp.col_bbox)
+                # (REGRESSION_BRANCH: lin_weak_sup holds the regression columns; unit_transfer_predictions_ex adds both in this one launch)
+                c.scores, bbox = bp.transfer(lin_sup, lin_weak_sup, sims["cls"], sims["bbox"], t, ft=lin_ft)
                 c.dy_sup = bp.ft_losses(c.scores, bbox, c.roi_cls, c.rois[:rs], c.roi_gt, c.losses[0:2], dt)
                 if c.metrics is not None:          # on the transferred logits, as the reference's FastRCNNOutputs sees them
                     ops.metrics_fastrcnn(c.scores, 0, rh.num_classes + 1, c.roi_cls, c.metrics[step_metrics.FAST_RCNN:step_metrics.FAST_RCNN + 5])

@@ -85,7 +85,7 @@ class WSROIHeadNoMeta(nn.Module):
         plans = {h: parse_terms(t, self.similarity_combination, len(self._base_classes)) for h, t in self.terms.items()}
         if reg:
             for p in plans.values():
-                check_regression_branch(p)
+                check_regression_branch(p, finetune=self.finetune)
         self._term_plans = (key, plans)
         return plans
 

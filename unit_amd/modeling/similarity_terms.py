@@ -112,10 +112,17 @@ def parse_terms(terms, combination, n_base):
                 product=combination == "Product")
 
 
-def check_regression_branch(plan):
-    """with WEAK_DETECTOR.REGRESSION_BRANCH the reference's evaluation() returns no list of refinement streams: the per-RoI terms fail"""
+FINETUNE_WITH_REGRESSION_BRANCH = (
+    "SupervisedDetectorOutputsFineTune with WEAK_DETECTOR.REGRESSION_BRANCH is not supported with these MODEL.ROI_HEADS.FINETUNE_TERMS (the shipped "
+    "defaults hold \"visual\"): set FINETUNE_TERMS.CLASSIFIER, FINETUNE_TERMS.BBOX and FINETUNE_TERMS.MASK to [\"lingual\"] or []. ")
+
+
+def check_regression_branch(plan, finetune=False):
+    """with WEAK_DETECTOR.REGRESSION_BRANCH the reference's evaluation() returns no list of refinement streams: the per-RoI terms fail.
+    finetune: the fine-tune ROI heads -- a fine-tune yaml that turns the switch on meets this refusal first, so it opens with the three lists to set"""
     from .inference import VISUAL_WITH_REGRESSION_BRANCH
+    pre = FINETUNE_WITH_REGRESSION_BRANCH if finetune else ""
     if plan.visual:          # computed whenever any head lists it, under either combination (roi_heads.py:248)
-        raise _unsupported(VISUAL_WITH_REGRESSION_BRANCH)
+        raise _unsupported(pre + VISUAL_WITH_REGRESSION_BRANCH)
     if plan.visualk and not plan.product:
-        raise _unsupported(VISUALK_WITH_REGRESSION_BRANCH)
+        raise _unsupported(pre + VISUALK_WITH_REGRESSION_BRANCH)

@@ -272,9 +272,7 @@ class _HeadsFn(torch.autograd.Function):
             lin_w_box = wh.group.fwd(box_feat)
             sims, lingual, keys = similarity_dict(rh, lin_w_box, want_ctx=True)
             t = class_roles(rh)
-            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, rh.num_classes, lin_weak[:rs], *wh.score_cols,
-                                                    sims["cls"], sims["bbox"], t["base"], t["novel"], t["role"], t["slot"], ft=lin_ft,
-                                                    fccol0=bp.col_cls, fbcol0=bp.col_bbox)
+            scores, bbox = bp.transfer(lin_sup, lin_weak[:rs], sims["cls"], sims["bbox"], t, ft=lin_ft)
             dy_sup = bp.ft_losses(scores, bbox, roi_cls, rois[:rs], roi_gt, losses[0:2], dtype)
             ft_ctx = (lin_sup, sims, lingual, keys, t, lin_w_box)
             if mask_on:
@@ -413,8 +411,9 @@ class _SupPredictFn(torch.autograd.Function):
                     sm = sm[None].expand(r, -1, -1)
                 sims.append(sm.detach().float().contiguous() if sm is not None else None)
             lin_ft = bp.group_ft.fwd(xc)
-            scores, bbox = ops.transfer_predictions(lin_sup, bp.col_cls, bp.col_bbox, k, lin_w, *wh.score_cols, sims[0], sims[1],
-                                                    t["base"], t["novel"], t["role"], t["slot"], ft=lin_ft, fccol0=bp.col_cls, fbcol0=bp.col_bbox)
+            # (REGRESSION_BRANCH: the weak deltas ride in the same launch, unit_transfer_predictions_ex; they are evaluated under no_grad
+            # in the reference, :490-494, so the backward below does not know them)
+            scores, bbox = bp.transfer(lin_sup, lin_w, sims[0], sims[1], t, ft=lin_ft)
             ctx.saved = (xc, lin_sup, sims)
         else:
             scores = ops.sup_scores(lin_sup, bp.col_cls, lin_w, *wh.score_cols, k + 1, t["novel_mask"])

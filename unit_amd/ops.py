@@ -1512,15 +1512,20 @@ def similarity(lin_weak, col0, n_oicr, ncls, base_dev, lingual, n_novel, visual_
 
 
 def transfer_predictions(lin, ccol0, bcol0, k, weak, wcol0, n_oicr, sim_cls, sim_bbox, base_dev, novel_dev, role_dev, slot_dev,
-                         ft=None, fccol0=0, fbcol0=0):
-    """-> (scores [R,K+1], bbox [R,4K]) of SupervisedDetectorOutputs*.forward (eval / fine-tune branches)."""
+                         ft=None, fccol0=0, fbcol0=0, wbcol0=None):
+    """-> (scores [R,K+1], bbox [R,4K]) of SupervisedDetectorOutputs*.forward (eval / fine-tune branches).
+    wbcol0: first column, in `weak`, of the weak head's [R, 4K] box deltas (REGRESSION_BRANCH under the fine-tune predictor), added to the
+    transferred deltas before `ft` in the same launch (unit_transfer_predictions_ex); None: the plain entry, as every call without it records."""
     r = lin.shape[0]
     scores = torch.empty((r, k + 1), dtype=torch.float32, device=lin.device)
     bbox = torch.empty((r, 4 * k), dtype=torch.float32, device=lin.device)
-    check(lib().unit_transfer_predictions(_p(lin), lin.shape[1], ccol0, bcol0, k, _p(weak), weak.shape[1] if weak is not None else 0, wcol0,
-                                          n_oicr, _p(ft), ft.shape[1] if ft is not None else 0, fccol0, fbcol0, _p(sim_cls), _p(sim_bbox),
-                                          _p(base_dev), base_dev.numel(), _p(novel_dev), novel_dev.numel(), _p(role_dev), _p(slot_dev),
-                                          _p(scores), k + 1, _p(bbox), 4 * k, r, _s()), "transfer_predictions")
+    head = (_p(lin), lin.shape[1], ccol0, bcol0, k, _p(weak), weak.shape[1] if weak is not None else 0, wcol0, n_oicr)
+    tail = (_p(ft), ft.shape[1] if ft is not None else 0, fccol0, fbcol0, _p(sim_cls), _p(sim_bbox), _p(base_dev), base_dev.numel(),
+            _p(novel_dev), novel_dev.numel(), _p(role_dev), _p(slot_dev), _p(scores), k + 1, _p(bbox), 4 * k, r, _s())
+    if wbcol0 is None:
+        check(lib().unit_transfer_predictions(*head, *tail), "transfer_predictions")
+    else:
+        check(lib().unit_transfer_predictions_ex(*head, int(wbcol0), *tail), "transfer_predictions_ex")
     return scores, bbox
 
 
