@@ -520,6 +520,16 @@ int unit_compact_detections(const float* boxes, const float* scores, const int* 
 int unit_boxes_to_rois5(const float* boxes, int B, int T, float* rois5, void* stream);
 int unit_gather_rows(const void* src, const int* idx, int B, int T, int rcap, int row_bytes, void* out, void* stream);
 int unit_gather_blocks(const void* src, int nb, int block_rows, int take, int row_bytes, void* out, void* stream);
+/* ---- pseudo-labelled RPN training: WeaklySupervisedRCNNRPN.forward, meta_arch/rcnn.py:594-609 ----
+ *   unit_pseudo_gt           rcnn.py:594-599: of the detections boxes [B][T][4] / scores [B][T] / cls int32 [B][T] / count int32 [B] of the
+ *                            weak images, row j < count[b] is kept iff multihot[b][cls] (uint8 [B][K]; a class outside [0, K) never is) and
+ *                            score > threshold (strict; NaN drops the row). gt_boxes [B][T][4] = the kept boxes at the front in detection
+ *                            order, zero rows behind; gt_count [B] = kept; kept_idx int32 [B][T] = their row numbers, -1 behind. T <= 1024;
+ *                            one workgroup per image, ballot + prefix compaction, nothing leaves the device
+ *   unit_gate_anchor_labels  rcnn.py:607-609: labels int8 [B][Ncap] of an image with gt_count[b] <= 0 become -1 (the image adds 0 to the loss) */
+int unit_pseudo_gt(const float* boxes, const float* scores, const int* cls, const int* count, const unsigned char* multihot, int B, int T, int K,
+                   float threshold, float* gt_boxes, int* gt_count, int* kept_idx, void* stream);
+int unit_gate_anchor_labels(signed char* labels, const int* gt_count, int B, int Ncap, void* stream);
 
 /* ---- a16 mask head: modeling/roi_heads/mask_head.py:16-37, roi_heads.py:654-710 (+ detectron2 mask_rcnn_loss/inference,
  * BitMasks.crop_and_resize). The 2x2/s2 ConvTranspose2d is one 1x1 GEMM with 4*Cout columns run by unit_conv2d_fwd. ---- */

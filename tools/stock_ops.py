@@ -45,7 +45,7 @@ class Log(TorchDispatchMode):
         return func(*args, **(kwargs or {}))
 
 
-mode = sys.argv[1] if len(sys.argv) > 1 else "s1"          # s1 | two_pass | x3 | s2 | mask | eval | eval_mask | clip (s1 with "norm" clipping + Nesterov)
+mode = sys.argv[1] if len(sys.argv) > 1 else "s1"          # s1 | two_pass | x3 | s2 | mask | eval | eval_mask | clip (s1 with "norm" clipping + Nesterov) | rpn (WeaklySupervisedRCNNRPN)
 if mode in ("s2",):
     cfg = config.voc_rcnn_c4_split1_ft(101)
 elif mode in ("mask", "eval_mask"):
@@ -54,11 +54,19 @@ else:
     cfg = config.voc_rcnn_c4_split1(101)
 cfg.MODEL.DEVICE = "cuda:0"
 cfg.SEED = 0
+if mode == "rpn":          # the pseudo-labelled RPN step; synthetic weights do not score 0.99: a threshold some detections pass
+    cfg.MODEL.META_ARCHITECTURE = "WeaklySupervisedRCNNRPN"
+    cfg.MODEL.PROPOSAL_GENERATOR.WEAK_RPN_SCORE_TRESHOLD = 0.1
+    cfg.SOLVER.BASE_LR = 1e-7          # (the warm-up steps must not train the random detector into "background everywhere")
 if mode == "clip":
     cfg.SOLVER.NESTEROV = True
     cfg.SOLVER.CLIP_GRADIENTS = config.CN(ENABLED=True, CLIP_TYPE="norm", CLIP_VALUE=0.05, NORM_TYPE=2.0)
 model = build_model(cfg)
 init_synthetic_weights(model, seed=1)
+if mode == "rpn":          # (class scores that differ between RoIs, as in tests/golden/gen_ref_step.py: the eval pass then detects something)
+    with torch.no_grad():
+        w = model.roi_heads.box_predictor.cls_score_delta.weight
+        w.copy_(torch.randn(w.shape, generator=torch.Generator().manual_seed(40)) * 0.05)
 model.train()
 model.compute_mode = "bf16x3" if mode == "x3" else "bf16"
 if mode == "two_pass":
@@ -81,6 +89,9 @@ elif mode in ("eval", "eval_mask"):
     inp = [{"image": x["image"].cuda(), "height": 600, "width": 1000} for x in sup]
 else:
     sup, weak = synthetic_batch(2, 2, seed=100)
+    if mode == "rpn":          # every class is a label of the weak images: whatever the synthetic weights detect can become pseudo ground truth
+        for x in weak:
+            x["instances"].gt_classes = torch.arange(20)
     batch = model.pack_batch(sup, weak)
 opt = FlatSGD(model, cfg) if model.training else None
 
@@ -104,3 +115,8 @@ print(f"[{mode}] ATen calls of one steady-state step / inference call that are n
 for (name, dev, site), n in sorted(log.calls.items(), key=lambda kv: (-kv[1], kv[0])):
     print(f"{n:4d}  {name:40s} {dev:5s} {site}")
 print("total", sum(log.calls.values()))
+if mode == "rpn":
+    st = model.forward_train(batch, early_backward=True)
+    model.backward_train(st)
+    print("pseudo ground-truth boxes per weak image:", st.weak["gt_count"].tolist(), "of", st.weak["det_count"].tolist(), "detections; losses",
+          dict(zip(model.loss_names, [round(v, 5) for v in st.losses.tolist()])))

@@ -98,7 +98,7 @@ def get_cfg():
     c.MODEL.RESNETS = CN(DEPTH=101, OUT_FEATURES=["res4"], NUM_GROUPS=1, WIDTH_PER_GROUP=64, STRIDE_IN_1X1=True,
                          RES2_OUT_CHANNELS=256, STEM_OUT_CHANNELS=64, NORM="FrozenBN", RES5_DILATION=1)
     c.MODEL.ANCHOR_GENERATOR = CN(NAME="DefaultAnchorGenerator", SIZES=[[32, 64, 128, 256, 512]], ASPECT_RATIOS=[[0.5, 1.0, 2.0]], OFFSET=0.0)
-    c.MODEL.PROPOSAL_GENERATOR = CN(NAME="WSRPN", MIN_SIZE=0, WEAK_RPN_SCORE_TRESHOLD=0.0)
+    c.MODEL.PROPOSAL_GENERATOR = CN(NAME="WSRPN", MIN_SIZE=0)
     c.MODEL.RPN = CN(HEAD_NAME="StandardRPNHead", IN_FEATURES=["res4"], BOUNDARY_THRESH=-1, IOU_THRESHOLDS=[0.3, 0.7],
                      IOU_LABELS=[0, -1, 1], BATCH_SIZE_PER_IMAGE=256, POSITIVE_FRACTION=0.5, BBOX_REG_LOSS_TYPE="smooth_l1",
                      BBOX_REG_LOSS_WEIGHT=1.0, BBOX_REG_WEIGHTS=(1.0, 1.0, 1.0, 1.0), SMOOTH_L1_BETA=0.0, LOSS_WEIGHT=1.0,
@@ -135,9 +135,11 @@ def add_config(cfg):
     _C.MODEL.ROI_HEADS.FINETUNE_TERMS = CN(CLASSIFIER=["lingual", "visual"], BBOX=["lingual", "visual"], MASK=["lingual", "visual"])
     _C.MODEL.ROI_HEADS.WEAK_CLASSIFIER_PROPOSAL_DIVISOR = 1
     _C.MODEL.ROI_HEADS.MULTI_BOX_HEAD = False
+    # read by WeaklySupervisedRCNNRPN only (configs/default_config.py:27-30; meta_arch/rcnn.py:594-609)
+    _C.MODEL.PROPOSAL_GENERATOR.WEAK_RPN_SCORE_TRESHOLD = 0.99
     _C.MODEL.ROI_HEADS.TRAIN_USING_WEAK = False
-    _C.MODEL.ROI_HEADS.TRAIN_PROPOSAL_REGRESSOR = False
-    _C.MODEL.ROI_HEADS.WEAK_PROPOSAL_DIVISOR = 1
+    _C.MODEL.ROI_HEADS.TRAIN_PROPOSAL_REGRESSOR = True
+    _C.MODEL.ROI_HEADS.WEAK_PROPOSAL_DIVISOR = 1.0
     _C.MODEL.ROI_HEADS.FAST_RCNN = CN(NAME="SupervisedDetectorOutputsBase")
     _C.MODEL.ROI_HEADS.FAST_RCNN.WEAK_DETECTOR = CN(
         NAME="WeakDetectorOutputsBase", DETECTOR_TEMP=1.0, CLASSIFIER_TEMP=1.0, REGRESSION_BRANCH=False, OICR_ITER=3,

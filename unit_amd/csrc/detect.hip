@@ -603,6 +603,74 @@ extern "C" int unit_compact_detections(const float* boxes, const float* scores, 
   return UNIT_OK;
 }
 
+// ---- pseudo ground truth of the weak images: WeaklySupervisedRCNNRPN.forward, meta_arch/rcnn.py:594-599 ---------------------------
+// The eval-mode detections of a weak image whose class is one of the image's labels (`labels_mask`, :594-595) and whose score is
+// strictly above WEAK_RPN_SCORE_TRESHOLD (`score_mask`, :596-597; a NaN score compares false and drops the row) become the image's
+// ground-truth boxes (:598), in detection order: the matcher's ties go to the first box. One workgroup per image, the kept rows of each
+// 256-row chunk ranked by ballot + popcount within a wave and a four-entry prefix over the waves: no atomics, the order is the input's.
+// Rows past gt_count[b] are zero boxes / index -1. T <= 1024; gt_boxes must not alias boxes.
+__global__ void __launch_bounds__(256) pseudo_gt_kernel(const float* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ cls,
+                                                        const int* __restrict__ count, const unsigned char* __restrict__ multihot, int K,
+                                                        float threshold, int T, float* __restrict__ gt_boxes, int* __restrict__ gt_count,
+                                                        int* __restrict__ kept_idx) {
+  __shared__ int wcnt[4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int c = min(max(count[b], 0), T);
+  int base = 0;
+  for (int j0 = 0; j0 < c; j0 += 256) {          // (c is the same for the whole workgroup: every thread reaches both barriers)
+    const int j = j0 + threadIdx.x;
+    const size_t s = (size_t)b * T + j;
+    bool keep = false;
+    if (j < c) {
+      int k = cls[s];
+      keep = k >= 0 && k < K && multihot[(size_t)b * K + k] != 0 && scores[s] > threshold;
+    }
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) wcnt[wid] = __popcll(bal);
+    __syncthreads();
+    int before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { int n = wcnt[w]; before += w < wid ? n : 0; all += n; }
+    if (keep) {
+      const size_t o = (size_t)b * T + base + before + __popcll(bal & ((1ull << lane) - 1ull));
+      *reinterpret_cast<f32x4*>(gt_boxes + 4 * o) = *reinterpret_cast<const f32x4*>(boxes + 4 * s);
+      kept_idx[o] = j;
+    }
+    base += all;
+    __syncthreads();          // wcnt is rewritten by the next chunk
+  }
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  for (int j = base + threadIdx.x; j < T; j += blockDim.x) {
+    const size_t o = (size_t)b * T + j;
+    *reinterpret_cast<f32x4*>(gt_boxes + 4 * o) = zero;
+    kept_idx[o] = -1;
+  }
+  if (threadIdx.x == 0) gt_count[b] = base;
+}
+extern "C" int unit_pseudo_gt(const float* boxes, const float* scores, const int* cls, const int* count, const unsigned char* multihot,
+                              int B, int T, int K, float threshold, float* gt_boxes, int* gt_count, int* kept_idx, void* stream) {
+  UNIT_CHECK_ARG(T >= 0 && T <= 1024, "pseudo_gt: T <= 1024");
+  UNIT_CHECK_ARG(K >= 1, "pseudo_gt: K >= 1");
+  UNIT_CHECK_ARG(gt_boxes != boxes, "pseudo_gt: gt_boxes needs a buffer of its own");
+  if (B == 0) return UNIT_OK;
+  pseudo_gt_kernel<<<B, 256, 0, (hipStream_t)stream>>>(boxes, scores, cls, count, multihot, K, threshold, T, gt_boxes, gt_count, kept_idx);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
+// A weak image without pseudo ground truth contributes 0 to the weak RPN losses (rcnn.py:607-609: the proposal generator is not called for
+// it): its sampled anchor labels -- all background, the matcher's answer to zero boxes -- become -1 (ignored) before the batched loss launch.
+__global__ void gate_anchor_labels_kernel(signed char* __restrict__ labels, const int* __restrict__ gt_count, int Ncap) {
+  const int b = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < Ncap && gt_count[b] <= 0) labels[(size_t)b * Ncap + i] = -1;
+}
+extern "C" int unit_gate_anchor_labels(signed char* labels, const int* gt_count, int B, int Ncap, void* stream) {
+  if (B == 0 || Ncap == 0) return UNIT_OK;
+  gate_anchor_labels_kernel<<<dim3(cdiv(Ncap, 256), B), 256, 0, (hipStream_t)stream>>>(labels, gt_count, Ncap);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
 // boxes [B][T][4] -> RoIAlign rows [B*T][5] = (image index, x0, y0, x1, y1)
 __global__ void boxes_to_rois5_kernel(const float* __restrict__ boxes, int T, long n, float* __restrict__ rois5) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -98,6 +98,9 @@ class GraphedStep:
         res4 a-d | res3) and launch each bucket's all-reduce eagerly between the replays, so that the collectives overlap the rest
         of the backward as in eager mode; False: one graph, one all-reduce of the whole flat gradient buffer after it"""
         import torch
+        refused = getattr(model, "step_modes_refused", None)          # a meta-architecture whose step is not capturable / recordable yet says why
+        if refused:
+            raise NotImplementedError(refused)
         self.model, self.optimizer, self.warmup_steps = model, optimizer, warmup_steps
         self.buckets = buckets if (buckets is not None and buckets.active) else None
         self.per_bucket = per_bucket

@@ -222,9 +222,7 @@ class Conv2d(_EpochOnLoad):
             side = ops.WGRAD_STREAM
             which = "_slab2" if acc else "_slab"
             if self.bias is not None and self.bias.requires_grad:       # (a conv without FrozenBN: the RPN's 3x3)
-                if self.bias.grad is None:
-                    self.bias.grad = torch.zeros_like(self.bias.data)
-                ops.bias_grad(dy_plain.reshape(-1, dy_plain.shape[-1]), self.cout, out=self.bias.grad, accumulate=acc)
+                self._bias_grad(dy_plain, acc)
             if self._plan.defer_wgrad(self, x, dy, st, acc):
                 return       # goes out with the rest of its gradient bucket in one grouped launch (multi.py)
 
@@ -250,13 +248,21 @@ class Conv2d(_EpochOnLoad):
             g = self._grad_krsc()
             for i, (xp, dp) in enumerate(zip(x, dy)):
                 ops.conv2d_wgrad(xp, dp, self.cout, self.k, self.k, st, self.pad, scale=self.scale, out=g, accumulate=acc or i > 0)
+            if self.bias is not None and self.bias.requires_grad:
+                self._bias_grad(dy_plain, acc)
             return
         gk = self._grad_krsc()
         ops.conv2d_wgrad(x, dy, self.cout, self.k, self.k, st, self.pad, scale=self.scale, out=gk, accumulate=acc)
         if self.bias is not None and self.bias.requires_grad:
-            if self.bias.grad is None:
-                self.bias.grad = torch.zeros_like(self.bias.data)
-            ops.bias_grad(dy_plain.reshape(-1, dy_plain.shape[-1]), self.cout, out=self.bias.grad, accumulate=acc)
+            self._bias_grad(dy_plain, acc)
+
+    def _bias_grad(self, dy, acc):
+        """column sums of dy into the bias gradient; dy an ops.Parts (two image groups, e.g. the RPN conv over the supervised and the
+        pseudo-labelled weak images): the parts' sums add up"""
+        if self.bias.grad is None:
+            self.bias.grad = torch.zeros_like(self.bias.data)
+        for i, d in enumerate(dy if isinstance(dy, ops.Parts) else (dy,)):
+            ops.bias_grad(d.reshape(-1, d.shape[-1]), self.cout, out=self.bias.grad, accumulate=acc or i > 0)
 
 
 def set_x3(module, on):
@@ -559,13 +565,19 @@ class LinearGroup:
         y = ops.conv2d(x2d.view(r, 1, 1, self.cin), self.wf, self.k, 1, 1, bias=self.bias, out_dtype=torch.float32, ldy=self.kp)
         return y.view(r, self.kp)
 
-    def bwd(self, x2d, dy2d, need_dx=True, mask_ref=None, out=None):
+    def bwd(self, x2d, dy2d, need_dx=True, mask_ref=None, out=None, accumulate=False):
         """dy [R,kp] (compute dtype, pad columns zero). Writes member .grad; returns dx [R,cin] (* (mask_ref > 0)); out: contiguous rows
-        of a larger [*, cin] matrix to write dx into."""
+        of a larger [*, cin] matrix to write dx into. accumulate: a SECOND group of rows within one step (the RPN predictors over the
+        pseudo-labelled weak images, behind the supervised ones): its gradients are added to what the first call wrote, on the same stream."""
         r = x2d.shape[0]
         gw, gb = self._fused_views("grad")
         trainable = any(m.weight.requires_grad for m in self.members)
-        if trainable and ops.WGRAD_DIRECT and ops.WGRAD_ACCUMULATE:
+        if trainable and accumulate and not ops.WGRAD_DIRECT:
+            if gw is None:
+                raise RuntimeError("LinearGroup.bwd(accumulate=True) needs the members' gradients in one flat buffer (flatten_parameters)")
+            ops.conv2d_wgrad(x2d.view(r, 1, 1, self.cin), dy2d.view(r, 1, 1, self.kp), self.kp, 1, 1, out=gw.view(self.kp, 1, 1, self.cin), accumulate=True)
+            ops.bias_grad(dy2d, self.k, out=gb, accumulate=True)
+        elif trainable and ops.WGRAD_DIRECT and (ops.WGRAD_ACCUMULATE or accumulate):
             # module-level training (modeling/train_modules.py): torch semantics -- a second backward before zero_grad(), or the reference's
             # per-image RPN calls (rcnn.py:601), ADD to .grad like the convs' direct weight gradients do (ADVICE r05)
             tmp = ops.conv2d_wgrad(x2d.view(r, 1, 1, self.cin), dy2d.view(r, 1, 1, self.kp), self.kp, 1, 1).view(self.kp, self.cin)

@@ -1,5 +1,6 @@
 """WeaklySupervisedRCNNNoMeta -- the MI355X counterpart of /root/reference/modeling/meta_arch/rcnn.py:431-542
 (training `forward` :433-491, `preprocess_image` :257-266, `inference` :493-542, `_postprocess` :411-429).
+WeaklySupervisedRCNNRPN (:544-654; the end of this file) is the same model with the weak batch training the RPN through pseudo ground truth.
 
 One training step = ONE explicit forward plan + ONE explicit backward plan over the HIP kernels (no autograd graph, no
 host sync): `forward_train` saves exactly the activations the backward needs, `backward_train` walks them in reverse and
@@ -332,15 +333,19 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         """RNG for subsample_labels: one permutation per image and per sampler (explicit-permutation contract). Drawn on the
         device by unit_perm_keys + the stable sort from (SEED + rank, a device-resident step counter): no torch.randperm, no
         host state -- a captured step draws fresh permutations on every replay."""
-        if self._gen is None:
-            seed = self.cfg.SEED if self.cfg.SEED >= 0 else 0
-            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
-            self._gen = (seed + rank, torch.zeros(1, dtype=torch.int64, device=self.device))
-        seed, counter = self._gen
+        seed, counter = self._rng()
         rpn = ops.random_permutations(n_sup, n_anchor, seed, counter, 0, self.device)
         roi = ops.random_permutations(n_sup, n_roi_cap, seed, counter, 1, self.device)
         ops.counter_bump(counter)
         return {"rpn": rpn, "roi": roi}
+
+    def _rng(self):
+        """(SEED + rank, the device-resident step counter) behind every permutation draw"""
+        if self._gen is None:
+            seed = self.cfg.SEED if self.cfg.SEED >= 0 else 0
+            rank = torch.distributed.get_rank() if torch.distributed.is_available() and torch.distributed.is_initialized() else 0
+            self._gen = (seed + rank, torch.zeros(1, dtype=torch.int64, device=self.device))
+        return self._gen
 
     # ------------------------------------------------------------------ the training step: forward plan
     def forward_train(self, batch, perms=None, early_backward=False, proposals=None):
@@ -359,7 +364,10 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         n_sup, n_weak = batch.n_sup, batch.n_weak
         n_img = n_sup + n_weak
         c.n_sup, c.n_weak = n_sup, n_weak
-        c.losses = ops.zeros(len(self.loss_names), torch.float32, self.device)
+        # (a subclass that has already written slots of this step's vector hands it over: WeaklySupervisedRCNNRPN)
+        c.losses = self.__dict__.pop("_step_losses", None)
+        if c.losses is None:
+            c.losses = ops.zeros(len(self.loss_names), torch.float32, self.device)
         c.metrics = None
         if self.collect_metrics:
             c.metrics = ops.zeros(step_metrics.SIZE, torch.int32, self.device)          # (the library's own fill: a recorded call, replayed with the step)
@@ -987,12 +995,16 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         if self._anchor is None or self._anchor.device != self.device:
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
         all_names = self.loss_names
-        names = all_names if batch.n_weak > 0 else [n for n in LOSS_NAMES if not (n.startswith("loss_oicr") or n == "loss_im_cls")]
+        names = self._returned_losses(batch)
         if step.mask_ctx is None:
             names = [n for n in names if n != "loss_mask"]
         used = torch.tensor([n in names for n in all_names], device=self.device)
         lv = _StepFn.apply(self._anchor, self, step, step.losses, used)
         return {n: lv[all_names.index(n)] for n in names}
+
+    def _returned_losses(self, batch):
+        """the keys of the dictionary `forward` returns for this batch (before the mask loss is dropped for a step without masks)"""
+        return self.loss_names if batch.n_weak > 0 else [n for n in LOSS_NAMES if not (n.startswith("loss_oicr") or n == "loss_im_cls")]
 
     def train_step(self, batch, optimizer=None, perms=None):
         """forward + backward (+ optimizer) without going through torch.autograd; returns the device loss vector."""
@@ -1006,6 +1018,132 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         from .inference import inference as _inf
         self.join_optimizer_tail()
         return _inf(self, batched_inputs, do_postprocess)
+
+
+WEAK_RPN_LOSSES = ["weak_loss_rpn_cls", "weak_loss_rpn_loc"]
+
+TRAIN_USING_WEAK_REFUSED = (
+    "MODEL.ROI_HEADS.TRAIN_USING_WEAK: True is not supported: the reference's branch (meta_arch/rcnn.py:580-587, :611-620) calls the ROI heads "
+    "with return_proposals=True, which this project refuses, and its precomputed-proposal form stops in a debugger (:640-641)")
+NOT_AN_RPN = ("WeaklySupervisedRCNNRPN trains the RPN on pseudo ground truth (meta_arch/rcnn.py:570-609): MODEL.PROPOSAL_GENERATOR.NAME "
+              "must name an RPN (WSRPN), got '{}'")
+STEP_MODES_REFUSED = (
+    "WeaklySupervisedRCNNRPN runs eagerly only: engine.GraphedStep / ReplayedStep do not take it yet. Missing: the weak half (a second "
+    "backbone pass, the eval-mode ROI heads, unit_pseudo_gt, and the second row group it hands to the RPN head's backward across the "
+    "supervised forward plan) has not been taken through a capture or a recording -- its buffers are not part of the static-input and "
+    "memory-pool contract of a captured step. Use TrainerNoMeta(use_graph=False, use_replay=False)")
+
+
+@META_ARCH_REGISTRY.register()
+class WeaklySupervisedRCNNRPN(WeaklySupervisedRCNNNoMeta):
+    """meta_arch/rcnn.py:544-654: image-level labels train the RPN. The supervised images take the step of WeaklySupervisedRCNNNoMeta
+    WITHOUT weak inputs (:644 passes weak_*=None to the ROI heads). The weak images go, without gradient, through the backbone (:558-560, a
+    pass of their own, padded to their own largest image), the training-mode RPN (:576) and the eval-mode ROI heads (:577-579); their
+    detections of a labelled class above WEAK_RPN_SCORE_TRESHOLD become pseudo ground truth (:594-599, unit_pseudo_gt) and the RPN loss
+    against it is added as weak_loss_rpn_cls / weak_loss_rpn_loc (:601-609, :622-624).
+
+    One batched loss launch restates the reference's per-image loop: image i with pseudo ground truth adds
+    RPN loss_i / (BATCH_SIZE_PER_IMAGE x 1) x loss_weight x threshold x WEAK_PROPOSAL_DIVISOR (the loc term x 0.0 instead when
+    TRAIN_PROPOSAL_REGRESSOR is off), an image without adds 0 (its anchor labels are gated to -1), the result is the mean over the weak
+    images: normaliser BATCH_SIZE_PER_IMAGE, weights loss_weight x threshold x divisor / n_weak. The gradient reaches the RPN head's three
+    convolutions only, as a second row group of the supervised images' RPN backward (StandardRPNHead.bwd): the gradient-bucket hooks see
+    the sum. Same state-dict keys, same inference as WeaklySupervisedRCNNNoMeta."""
+
+    step_modes_refused = STEP_MODES_REFUSED
+
+    def __init__(self, cfg, thing_classes=None):
+        from .inference import UnsupportedConfig
+        from .rpn import WSRPN
+        if cfg.MODEL.ROI_HEADS.TRAIN_USING_WEAK:
+            raise UnsupportedConfig(TRAIN_USING_WEAK_REFUSED)
+        name = cfg.MODEL.PROPOSAL_GENERATOR.NAME
+        if name not in PROPOSAL_GENERATOR_REGISTRY or not issubclass(PROPOSAL_GENERATOR_REGISTRY.get(name), WSRPN):
+            raise UnsupportedConfig(NOT_AN_RPN.format(name))
+        super().__init__(cfg, thing_classes)
+        self.weak_rpn_score_threshold = float(cfg.MODEL.PROPOSAL_GENERATOR.WEAK_RPN_SCORE_TRESHOLD)
+        self.train_proposal_regressor = bool(cfg.MODEL.ROI_HEADS.TRAIN_PROPOSAL_REGRESSOR)
+        self.weak_proposal_divisor = float(cfg.MODEL.ROI_HEADS.WEAK_PROPOSAL_DIVISOR)
+        if int(cfg.TEST.DETECTIONS_PER_IMAGE) > 256:
+            raise UnsupportedConfig("WeaklySupervisedRCNNRPN: TEST.DETECTIONS_PER_IMAGE > 256 -- the detections of a weak image are its candidate "
+                                    "ground-truth boxes and the anchor matcher (unit_iou_match) holds at most 256 per image")
+
+    @property
+    def loss_names(self):
+        """the base class's slots, then weak_loss_rpn_cls / weak_loss_rpn_loc"""
+        return super().loss_names + WEAK_RPN_LOSSES
+
+    def _returned_losses(self, batch):
+        # rcnn.py:644: the ROI heads never see the weak batch -> no loss_im_cls / loss_oicr_* (nor the weak head's regression losses);
+        # :630-632: without weak inputs no weak keys
+        names = [n for n in LOSS_NAMES if not (n.startswith("loss_oicr") or n == "loss_im_cls")]
+        return names + (WEAK_RPN_LOSSES if batch.n_weak > 0 else [])
+
+    def _clear_unproduced(self, c):
+        # No step of this class produces a gradient for the weak heads (rcnn.py:644 keeps the weak batch from the ROI heads). Their ranges of
+        # the flat gradient buffer are zero from its allocation and nothing ever writes them: cleared once per buffer, not once per step
+        if self.__dict__.get("_cleared_store") is not self.store:
+            super()._clear_unproduced(c)
+            self._cleared_store = self.store
+
+    def weak_permutations(self, n_weak, n_anchor):
+        """one anchor-sampling permutation per weak image (`weak_rpn` of the explicit-permutation contract), drawn on the device from the
+        same (seed, step counter) as the step's other draws under a stream id of its own"""
+        seed, counter = self._rng()
+        return ops.random_permutations(n_weak, n_anchor, seed, counter, 2, self.device)
+
+    def forward_train(self, batch, perms=None, early_backward=False, proposals=None):
+        """-> the base class's step context of the SUPERVISED images (rcnn.py:644), its loss vector two slots longer; `c.weak` holds the weak
+        half's device tensors (pseudo ground truth, kept detection indices, anchor labels), None without weak images"""
+        rpn = self.proposal_generator
+        rpn.rpn_head.second_group = None
+        self.__dict__.pop("_step_losses", None)
+        n_sup, n_weak = batch.n_sup, batch.n_weak
+        if n_sup == 0:
+            raise ValueError("WeaklySupervisedRCNNRPN.forward needs supervised images (rcnn.py:550 preprocesses batched_inputs unconditionally)")
+        if proposals is not None:
+            raise NotImplementedError("WeaklySupervisedRCNNRPN: precomputed proposals -- the reference's branch (rcnn.py:633-642) has no weak RPN loss")
+        sup_batch = PackedBatch(batch.images[:n_sup], batch.gt_boxes, batch.gt_classes, batch.gt_count, n_sup, None, batch.gt_masks)
+        if n_weak == 0:
+            c = super().forward_train(sup_batch, perms, early_backward)
+            c.weak = None
+            return c
+        if self._x3:
+            raise NotImplementedError("WeaklySupervisedRCNNRPN: compute_mode \"bf16x3\" is not wired through the two-group RPN backward; use \"bf16\" or \"fp32\"")
+        self._ensure_ready()
+        self.join_optimizer_tail()          # the weak pass reads every weight now: no optimizer tail beside it
+        dt = self.compute_dtype
+        from .inference import roi_heads_inference
+        losses = ops.zeros(len(self.loss_names), torch.float32, self.device)
+        # ---- weak half (rcnn.py:557-609), nothing of it saved for a backward but the RPN head's two activations
+        xw, sizes_w = ops.preprocess_images(batch.images[n_sup:], self._pixel_mean, self._pixel_std, dt, 8, self.normalize_images)
+        feat_w, _ = self.backbone.fwd(xw)
+        head_w, rpn_ctx_w = rpn.rpn_head.fwd(feat_w, save=True)
+        anchors_w = rpn.anchor_generator.grid(feat_w.shape[1], feat_w.shape[2])
+        hw_w = self._sizes_on_device(sizes_w)
+        props, _, pcount = rpn.predict_proposals(head_w, anchors_w, hw_w, True)          # training-mode top-k: only roi_heads is in eval (:577)
+        boxes, scores, classes, _, count, _ = roi_heads_inference(self.roi_heads, feat_w, props, pcount, hw_w, dt, with_mask=False)
+        gt_boxes, gt_count, kept = ops.pseudo_gt(boxes, scores, classes, count, batch.multihot, self.weak_rpn_score_threshold)
+        wperm = perms.get("weak_rpn") if perms is not None else None
+        if wperm is None:
+            wperm = self.weak_permutations(n_weak, anchors_w.shape[0])
+        labels_w, match_w, _ = rpn.label_and_sample_anchors(anchors_w, gt_boxes, gt_count, wperm)
+        ops.gate_anchor_labels(labels_w, gt_count)          # an image without pseudo ground truth adds 0 (:607-609)
+        f = self.weak_rpn_score_threshold * self.weak_proposal_divisor / n_weak
+        w_loc = rpn.loss_weight["loss_rpn_loc"] * f if self.train_proposal_regressor else 0.0          # (:606: x 0.0)
+        _, dhead_w = ops.rpn_loss(head_w, rpn.num_anchors, rpn.num_anchors, labels_w, match_w, gt_boxes, anchors_w, rpn.batch_size_per_image, dt,
+                                  loss_out=losses[len(losses) - 2:], weights=(rpn.loss_weight["loss_rpn_cls"] * f, w_loc),
+                                  loss_type=rpn.box_reg_loss_type, beta=rpn.smooth_l1_beta)
+        if any(p.requires_grad for p in rpn.rpn_head.parameters()):
+            group = (rpn_ctx_w[0], rpn_ctx_w[1], dhead_w)
+            if self._streams_on():          # the RPN backward may run on the RPN-branch stream, its weight gradients on theirs
+                for t in group + (losses,):
+                    t.record_stream(self._rpn_stream)
+                    t.record_stream(self._wgrad_stream)
+            rpn.rpn_head.second_group = group          # consumed by the step's one RPN-head backward
+        self._step_losses = losses
+        c = super().forward_train(sup_batch, perms, early_backward)
+        c.weak = dict(gt_boxes=gt_boxes, gt_count=gt_count, kept=kept, anchor_labels=labels_w, det_count=count, det_scores=scores, det_classes=classes)
+        return c
 
 
 def build_model(cfg, thing_classes=None):

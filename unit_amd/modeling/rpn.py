@@ -25,6 +25,7 @@ class StandardRPNHead(nn.Module):
             nn.init.normal_(l.weight, std=0.01)
             nn.init.constant_(l.bias, 0)
         self.pred = LinearGroup([self.objectness_logits, self.anchor_deltas])
+        self.second_group = None          # (feat, t, dhead) of a second image group for the NEXT bwd() -- consumed there
 
     def prepare(self, dtype, version):
         self.conv.prepare(dtype, version)
@@ -51,7 +52,19 @@ class StandardRPNHead(nn.Module):
         n, h, w, c = feat.shape
         t2 = t.view(n * h * w, c)
         dt = self.pred.bwd(t2, dhead.view(n * h * w, self.pred.kp), mask_ref=t2).view(n, h, w, c)
-        self.conv.wgrad(feat, dt)
+        second, self.second_group = self.second_group, None
+        if second is not None:
+            # WeaklySupervisedRCNNRPN: the pseudo-labelled weak images are a second group of rows of the SAME three weight gradients
+            # (rcnn.py:601 calls the proposal generator once more per weak image and autograd adds). The predictors' gradient is added by
+            # a second launch on this stream, the 3x3 conv takes the two groups as the parts of one weight gradient (one reduction), and
+            # only the supervised group continues into the backbone: the weak feature map was computed without gradient (:558-560).
+            feat_w, t_w, dhead_w = second
+            nw, hw_, ww, _ = feat_w.shape
+            t2w = t_w.view(nw * hw_ * ww, c)
+            dt_w = self.pred.bwd(t2w, dhead_w.view(nw * hw_ * ww, self.pred.kp), mask_ref=t2w, accumulate=True).view(nw, hw_, ww, c)
+            self.conv.wgrad(ops.Parts((feat, feat_w)), ops.Parts((dt, dt_w)))
+        else:
+            self.conv.wgrad(feat, dt)
         return self.conv.dgrad(dt, (h, w))
 
 

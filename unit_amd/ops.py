@@ -1663,6 +1663,29 @@ def compact_detections(boxes, sc, cls, roi, cnt, nonempty=None, masks=None):
     return ob, osc, ocls, oroi, om, kept
 
 
+def pseudo_gt(boxes, scores, classes, count, multihot, threshold):
+    """rcnn.py:594-599 (unit_pseudo_gt): detections boxes [N,T,4] / scores [N,T] / classes int32 [N,T] / count int32 [N] of the weak images,
+    multihot uint8 [N,K] -> (gt_boxes [N,T,4]: the rows whose class is a label of the image and whose score is > threshold, at the front in
+    detection order, zeros behind; gt_count int32 [N]; kept_idx int32 [N,T]: their row numbers, -1 behind). Everything stays on the device."""
+    n, t = scores.shape
+    assert classes.dtype == torch.int32 and count.dtype == torch.int32 and multihot.dtype == torch.uint8 and multihot.shape[0] == n
+    assert boxes.is_contiguous() and scores.is_contiguous() and classes.is_contiguous() and multihot.is_contiguous()
+    dev = boxes.device
+    gt_boxes = torch.empty((n, t, 4), dtype=torch.float32, device=dev)
+    gt_count = torch.empty((n,), dtype=torch.int32, device=dev)
+    kept = torch.empty((n, t), dtype=torch.int32, device=dev)
+    check(lib().unit_pseudo_gt(_p(boxes), _p(scores), _p(classes), _p(count), _p(multihot), n, t, multihot.shape[1], float(threshold),
+                               _p(gt_boxes), _p(gt_count), _p(kept), _s()), "pseudo_gt")
+    return gt_boxes, gt_count, kept
+
+
+def gate_anchor_labels(labels, gt_count):
+    """in place: the int8 anchor labels [N,Ncap] of every image with gt_count <= 0 become -1 (rcnn.py:607-609: such an image adds 0)"""
+    assert labels.dtype == torch.int8 and labels.is_contiguous() and gt_count.dtype == torch.int32
+    check(lib().unit_gate_anchor_labels(_p(labels), _p(gt_count), labels.shape[0], labels.shape[1], _s()), "gate_anchor_labels")
+    return labels
+
+
 def boxes_to_rois5(boxes):
     """[B,T,4] -> [B*T,5] RoIAlign rows (image index, box)"""
     b, t = boxes.shape[0], boxes.shape[1]
