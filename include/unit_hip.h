@@ -39,6 +39,18 @@ int unit_resize_u8_pass(const unsigned char* src, int H, int W, int C, int axis,
                         int out_size, unsigned char* dst, void* stream);
 int unit_preprocess_u8(const unsigned char* img_hwc, int C, int H, int W, int hflip, const float* mean3, const float* std3,
                        float prescale, void* out_nhwc, int out_dtype, int Hmax, int Wmax, int Cpad, void* stream);
+/* ---- test-time augmentation, the views: WeaklySupervisedRCNNNoMeta._init_tta_fn, modeling/meta_arch/rcnn.py:209-248 ----
+ * unit_image_chw_to_u8: `image.permute(1, 2, 0).numpy().astype(np.uint8)` (:216-218). img_chw fp32 [C][H][W] (src_u8 = 0) or uint8 (src_u8 = 1,
+ * a pure transpose) -> out_hwc uint8 [H][W][C]. The cast truncates toward zero; the contract is values in [0, 256): outside it numpy's own
+ * result is platform-defined and this one is not specified.
+ * unit_tta_boxes: the proposals of V views in one launch (:226, :240) -- Detectron2's ResizeTransform.apply_box and HFlipTransform.apply_box
+ * on the float32 box array, each followed by .clip(min=0), in float32 as numpy computes them: x' = max(x * sx, 0), y' = max(y * sy, 0); for a
+ * flipped view x0'' = max(W - x1', 0), x1'' = max(W - x0', 0). No clip to the maximum. props [P][4]; count: device int (NULL: P rows);
+ * views: device float [V][4] = (sx, sy, flip != 0, W) with sx = float32(new_w / w), sy = float32(new_h / h), the quotients taken in double by
+ * the caller, W = float32(new_w); out [V][Pcap][4], rows >= min(*count, P) written as zeros. A NaN coordinate becomes 0 (numpy keeps it).
+ * props, views and out 16-byte aligned. */
+int unit_image_chw_to_u8(const void* img_chw, int src_u8, int C, int H, int W, unsigned char* out_hwc, void* stream);
+int unit_tta_boxes(const float* props, const int* count, int P, int Pcap, const float* views, int V, float* out, void* stream);
 /* NCHW fp32 <-> NHWC converters for the plugin boundary (reference tensors are NCHW fp32) */
 int unit_nchw_to_nhwc(const float* x, void* y, int dtype, int N, int C, int H, int W, int Cp, void* stream);
 int unit_nhwc_to_nchw(const void* x, int dtype, float* y, int N, int C, int H, int W, int Cp, void* stream);
@@ -308,6 +320,8 @@ int unit_rpn_decode_select(const float* head, long head_batch_stride, int ld, in
                            float scale_clamp, float min_size, float* cand_boxes, float* cand_scores, int* cand_count, void* stream);
 /* entries behind keep_count[b] are written too: keep_idx = -1, out_boxes / out_scores = 0 */
 size_t unit_nms_workspace_bytes(int B, int cap);
+/* the largest `cap` unit_nms accepts (the TTA path sizes the detection candidates to Rcap * K and refuses beyond this instead of cutting) */
+int unit_nms_max_candidates(void);
 int unit_nms(const float* boxes_sorted, const float* scores_sorted, const int* count, int B, int cap, float thresh, int max_keep,
              int* keep_idx, int* keep_count, float* out_boxes, float* out_scores, void* workspace, size_t workspace_bytes,
              void* stream);
@@ -496,6 +510,15 @@ int unit_similarity_bwd_ex(const float* lin_weak, int ld, int col0, int n_oicr, 
                            int product, const float* dsim, void* dlin, int dlin_dtype, int ldl, int dcol0, int R, void* stream);
 /* ---- a15 detections: fast_rcnn.py:455-468 -> detectron2 fast_rcnn_inference; rcnn.py:411-429 detector_postprocess ---- */
 int unit_softmax_rows(const float* x, int ld, int ncls, float* y, int ldy, int R, void* stream);
+/* test-time augmentation, combining the views: meta_arch/rcnn.py:516 `torch.stack(cls_pred_scores).sum(0)` (each entry the softmax of one
+ * view's scores, fast_rcnn.py:456-458; the sum is NOT renormalised) and :524 `torch.stack(cls_pred_boxes).mean(0)` (the flipped views' dx
+ * averaged as they are). One call adds the predictions of n_in = 1 or 2 consecutive views, v and v + 1, of n, in view order: scores
+ * [.., lds] (K + 1 columns from scol0) and deltas [.., ldd] (4K columns), R rows per view, the second view view_rows rows behind the first.
+ * probs_sum [R][K+1] and delta_sum [R][4K] are "=" at view 0 and "+=" after it; each softmax is the device function unit_softmax_rows uses.
+ * With the last view (v + n_in == n) delta_mean [R][4K] = delta_sum / n, a division. Rows >= *count (device int, NULL: R): zeros, written with
+ * view 0 (delta_mean: with the last view). ldd a multiple of 4, the delta buffers 16-byte aligned, delta_mean != delta_sum. */
+int unit_tta_accumulate(const float* scores, int lds, int scol0, const float* deltas, int ldd, long view_rows, int n_in, int K, int R,
+                        const int* count, int v, int n, float* probs_sum, float* delta_sum, float* delta_mean, void* stream);
 int unit_detection_candidates(const float* probs, int ldp, const float* deltas, int ldd, const float* props, const int* pcount, int B,
                               int Rcap, int K, const float* weights4, float scale_clamp, const float* image_hw_dev, float score_thresh,
                               int cap, float* cand_boxes, float* cand_scores, int* cand_class, int* cand_roi, int* cand_count,

@@ -121,7 +121,11 @@ def get_cfg():
                   WEIGHT_DECAY_BIAS=1e-4, BIAS_LR_FACTOR=1.0, STEPS=(12000, 24000), MAX_ITER=30000, WARMUP_ITERS=100,
                   WARMUP_FACTOR=1.0 / 1000, GAMMA=0.1, CHECKPOINT_PERIOD=500)
     c.SOLVER.CLIP_GRADIENTS = CN(ENABLED=False, CLIP_TYPE="value", CLIP_VALUE=1.0, NORM_TYPE=2.0)          # "value" | "norm" | "full_model"; 1.0 | 2.0 | inf
-    c.TEST = CN(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0, AUG=CN(ENABLED=False))
+    # TEST.AUG: the reference's multi-scale + flip test-time augmentation (configs/default_config.py:97-101; modeling/inference.py). MIN_SIZES,
+    # MAX_SIZE and FLIP carry the reference's defaults; ENABLED stays False here although the reference's default is True: every shipped yaml sets
+    # False, and turning the default on would change what an existing configuration computes.
+    c.TEST = CN(DETECTIONS_PER_IMAGE=100, EVAL_PERIOD=0,
+                AUG=CN(ENABLED=False, MIN_SIZES=(480, 576, 688, 864, 1200), MAX_SIZE=2000, FLIP=True))
     c.SEED = -1
     add_config(c)
     return c

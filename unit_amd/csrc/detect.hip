@@ -347,20 +347,92 @@ extern "C" int unit_similarity_bwd(const float* lin_weak, int ld, int col0, int 
   return UNIT_OK;
 }
 
-// row softmax (predict_probs: F.softmax(scores, dim=-1))
-__global__ void softmax_rows_kernel(const float* __restrict__ x, int ld, int ncls, float* __restrict__ y, int ldy, int R) {
-  int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  const float* p = x + (size_t)r * ld;
+// row softmax (predict_probs: F.softmax(scores, dim=-1)): the row's maximum and sum of exponentials, then one probability per column.
+// unit_softmax_rows and unit_tta_accumulate share these two functions: the same operations in the same order, the same bits.
+__device__ __forceinline__ void softmax_row_stats(const float* __restrict__ p, int ncls, float* mx_out, float* se_out) {
   float mx = -INFINITY;
   for (int c = 0; c < ncls; ++c) mx = fmaxf(mx, p[c]);
   float se = 0.f;
   for (int c = 0; c < ncls; ++c) se += expf(p[c] - mx);
-  for (int c = 0; c < ncls; ++c) y[(size_t)r * ldy + c] = expf(p[c] - mx) / se;
+  *mx_out = mx; *se_out = se;
+}
+__device__ __forceinline__ float softmax_row_prob(float x, float mx, float se) { return expf(x - mx) / se; }
+
+__global__ void softmax_rows_kernel(const float* __restrict__ x, int ld, int ncls, float* __restrict__ y, int ldy, int R) {
+  int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const float* p = x + (size_t)r * ld;
+  float mx, se;
+  softmax_row_stats(p, ncls, &mx, &se);
+  for (int c = 0; c < ncls; ++c) y[(size_t)r * ldy + c] = softmax_row_prob(p[c], mx, se);
 }
 extern "C" int unit_softmax_rows(const float* x, int ld, int ncls, float* y, int ldy, int R, void* stream) {
   if (R == 0) return UNIT_OK;
   softmax_rows_kernel<<<cdiv(R, 128), 128, 0, (hipStream_t)stream>>>(x, ld, ncls, y, ldy, R);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
+// ---- test-time augmentation, combining the views: WeaklySupervisedRCNNNoMeta.inference, meta_arch/rcnn.py:511-524 -------------------
+//   cls_pred_scores = torch.stack(cls_pred_scores).sum(0)   (:516; each entry softmax(scores) of one view, fast_rcnn.py:456-458; NOT renormalised)
+//   cls_pred_boxes  = torch.stack(cls_pred_boxes).mean(0)    (:524; the flipped views' dx are averaged as they are)
+// One launch takes the predictions of n_in (1 or 2) consecutive views, v and v + 1, and adds them in view order: "=" for view 0, "+=" after it.
+// With the last view delta_sum / n is written as delta_mean -- a division, as torch's mean is sum / n. The first R threads own one row of
+// probs_sum each (the softmax is serial over the K + 1 columns, as in softmax_rows_kernel), the R * K after them one f32x4 of deltas each.
+// Rows >= *count: zeros are written with view 0 (and to delta_mean with the last view), nothing is read. Latency-sized: a few hundred KB.
+__global__ void __launch_bounds__(256) tta_accumulate_kernel(const float* __restrict__ scores, int lds_, int scol0, const float* __restrict__ deltas,
+                                                             int ldd, long view_rows, int n_in, int K, int R, const int* __restrict__ count, int v,
+                                                             int n, float* __restrict__ probs_sum, float* __restrict__ delta_sum,
+                                                             float* __restrict__ delta_mean) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const int ncls = K + 1;
+  const int live = count ? min(max(*count, 0), R) : R;
+  const bool last = v + n_in == n;
+  if (idx < R) {
+    const int r = (int)idx;
+    float* o = probs_sum + (size_t)r * ncls;
+    if (r >= live) {
+      if (v == 0) for (int c = 0; c < ncls; ++c) o[c] = 0.f;
+      return;
+    }
+    for (int j = 0; j < n_in; ++j) {
+      const float* p = scores + ((size_t)j * view_rows + r) * lds_ + scol0;
+      float mx, se;
+      softmax_row_stats(p, ncls, &mx, &se);
+      if (v + j == 0) for (int c = 0; c < ncls; ++c) o[c] = softmax_row_prob(p[c], mx, se);
+      else for (int c = 0; c < ncls; ++c) o[c] = o[c] + softmax_row_prob(p[c], mx, se);
+    }
+    return;
+  }
+  idx -= R;
+  if (idx >= (long)R * K) return;
+  const int r = (int)(idx / K), k = (int)(idx - (long)r * K);
+  f32x4* s = reinterpret_cast<f32x4*>(delta_sum + (size_t)r * 4 * K + 4 * k);
+  f32x4* m = reinterpret_cast<f32x4*>(delta_mean + (size_t)r * 4 * K + 4 * k);
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  if (r >= live) {
+    if (v == 0) *s = zero;
+    if (last) *m = zero;
+    return;
+  }
+  f32x4 acc = *reinterpret_cast<const f32x4*>(deltas + (size_t)r * ldd + 4 * k);
+  if (v != 0) acc = *s + acc;
+  if (n_in == 2) acc = acc + *reinterpret_cast<const f32x4*>(deltas + ((size_t)view_rows + r) * ldd + 4 * k);
+  *s = acc;
+  if (last) { const float d = (float)n; *m = f32x4{acc[0] / d, acc[1] / d, acc[2] / d, acc[3] / d}; }
+}
+extern "C" int unit_tta_accumulate(const float* scores, int lds, int scol0, const float* deltas, int ldd, long view_rows, int n_in, int K, int R,
+                                   const int* count, int v, int n, float* probs_sum, float* delta_sum, float* delta_mean, void* stream) {
+  UNIT_CHECK_ARG(K >= 1 && R >= 0 && (n_in == 1 || n_in == 2), "tta_accumulate: K >= 1, one or two views per launch");
+  UNIT_CHECK_ARG(n >= 1 && v >= 0 && v + n_in <= n, "tta_accumulate: views v .. v + n_in - 1 of n");
+  UNIT_CHECK_ARG(scol0 >= 0 && lds >= scol0 + K + 1 && ldd >= 4 * K && ldd % 4 == 0, "tta_accumulate: row strides (deltas: a multiple of 4 floats)");
+  UNIT_CHECK_ARG(n_in == 1 || view_rows >= R, "tta_accumulate: the second view starts view_rows >= R rows behind the first");
+  UNIT_CHECK_ARG(((uintptr_t)deltas | (uintptr_t)delta_sum | (uintptr_t)delta_mean) % 16 == 0, "tta_accumulate: 16-byte aligned delta buffers");
+  UNIT_CHECK_ARG(delta_mean != delta_sum, "tta_accumulate: delta_mean needs a buffer of its own");
+  if (R == 0) return UNIT_OK;
+  long threads = (long)R + (long)R * K;
+  tta_accumulate_kernel<<<cdiv(threads, 256L), 256, 0, (hipStream_t)stream>>>(scores, lds, scol0, deltas, ldd, view_rows, n_in, K, R, count, v, n,
+                                                                            probs_sum, delta_sum, delta_mean);
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }

@@ -91,3 +91,61 @@ extern "C" int unit_preprocess_u8(const unsigned char* img_hwc, int C, int H, in
   UNIT_LAUNCH_CHECK();
   return UNIT_OK;
 }
+
+// ---- test-time augmentation, the views: WeaklySupervisedRCNNNoMeta._init_tta_fn, modeling/meta_arch/rcnn.py:209-248 -------------------
+// `image.permute(1, 2, 0).numpy().astype(np.uint8)` (:216-218): CHW -> uint8 HWC, the cast truncating toward zero. Contract: values in
+// [0, 256) -- outside it numpy's own result is platform-defined. A uint8 source is a pure transpose. One thread per pixel, coalesced reads
+// of each plane along x.
+template <typename T>
+__global__ void image_chw_to_u8_kernel(const T* __restrict__ img, int C, int H, int W, unsigned char* __restrict__ out) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long hw = (long)H * W;
+  if (idx >= hw) return;
+  for (int c = 0; c < C; ++c) out[idx * C + c] = (unsigned char)(int)img[(size_t)c * hw + idx];
+}
+extern "C" int unit_image_chw_to_u8(const void* img_chw, int src_u8, int C, int H, int W, unsigned char* out_hwc, void* stream) {
+  UNIT_CHECK_ARG(C >= 1 && C <= 4 && H >= 0 && W >= 0, "image_chw_to_u8: 1..4 channels");
+  long n = (long)H * W;
+  if (n == 0) return UNIT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (src_u8) image_chw_to_u8_kernel<unsigned char><<<cdiv(n, 256L), 256, 0, st>>>((const unsigned char*)img_chw, C, H, W, out_hwc);
+  else image_chw_to_u8_kernel<float><<<cdiv(n, 256L), 256, 0, st>>>((const float*)img_chw, C, H, W, out_hwc);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
+// The proposals of every view (:226, :240): Detectron2's ResizeTransform.apply_box and HFlipTransform.apply_box on the float32 box array,
+// each followed by `.clip(min=0)`, in float32 exactly as numpy computes them:
+//   x' = max(x * sx, 0), y' = max(y * sy, 0)            sx = float32(new_w / w), sy = float32(new_h / h): the quotient taken in double by the caller
+//   flipped twin: x0'' = max(W - x1', 0), x1'' = max(W - x0', 0)      W = float32(new_w). There is no clip to the maximum.
+// views [V][4] = (sx, sy, flip != 0, W). Every product is rounded and clipped BEFORE the subtraction reads it -- the fmaxf between the two
+// keeps the compiler from fusing them into an fma (the library is built with -ffp-contract=off as well). Rows >= *count are zeros.
+// One thread per (view, row), one 16-byte load and one 16-byte store.
+__global__ void __launch_bounds__(256) tta_boxes_kernel(const float* __restrict__ props, const int* __restrict__ count, int P, int Pcap,
+                                                        const float* __restrict__ views, int V, float* __restrict__ out) {
+  long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long)V * Pcap) return;
+  const int v = (int)(idx / Pcap), r = (int)(idx - (long)v * Pcap);
+  const int live = count ? min(max(*count, 0), P) : P;
+  f32x4 o = {0.f, 0.f, 0.f, 0.f};
+  if (r < live) {
+    const f32x4 b = *reinterpret_cast<const f32x4*>(props + 4 * (size_t)r);
+    const f32x4 t = *reinterpret_cast<const f32x4*>(views + 4 * (size_t)v);
+    float x0 = fmaxf(b[0] * t[0], 0.f), y0 = fmaxf(b[1] * t[1], 0.f), x1 = fmaxf(b[2] * t[0], 0.f), y1 = fmaxf(b[3] * t[1], 0.f);
+    if (t[2] != 0.f) {
+      const float fx0 = fmaxf(t[3] - x1, 0.f), fx1 = fmaxf(t[3] - x0, 0.f);
+      x0 = fx0; x1 = fx1;
+    }
+    o = f32x4{x0, y0, x1, y1};
+  }
+  *reinterpret_cast<f32x4*>(out + 4 * (size_t)idx) = o;
+}
+extern "C" int unit_tta_boxes(const float* props, const int* count, int P, int Pcap, const float* views, int V, float* out, void* stream) {
+  UNIT_CHECK_ARG(P >= 0 && Pcap >= P && V >= 0, "tta_boxes: 0 <= P <= Pcap");
+  UNIT_CHECK_ARG(((uintptr_t)props | (uintptr_t)views | (uintptr_t)out) % 16 == 0, "tta_boxes: 16-byte aligned buffers");
+  long n = (long)V * Pcap;
+  if (n == 0) return UNIT_OK;
+  tta_boxes_kernel<<<cdiv(n, 256L), 256, 0, (hipStream_t)stream>>>(props, count, P, Pcap, views, V, out);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}

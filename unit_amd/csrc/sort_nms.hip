@@ -735,6 +735,8 @@ __global__ void __launch_bounds__(640) nms_scan_dq_kernel(const float* __restric
 }
 
 extern "C" size_t unit_nms_workspace_bytes(int B, int cap) { return (size_t)B * cap * ((cap + 63) / 64) * 8; }
+// the largest `cap` unit_nms takes: one scan thread per 64-candidate word of the "removed" bitmap (the check below)
+extern "C" int unit_nms_max_candidates(void) { return NMS_SCAN_THREADS * 64; }
 
 extern "C" int unit_nms(const float* boxes_sorted, const float* scores_sorted, const int* count, int B, int cap,
                         float thresh, int max_keep, int* keep_idx, int* keep_count, float* out_boxes, float* out_scores,

@@ -1017,7 +1017,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
     def inference(self, batched_inputs, detected_instances=None, do_postprocess=True, return_similarity=False):
         from .inference import inference as _inf
         self.join_optimizer_tail()
-        return _inf(self, batched_inputs, do_postprocess)
+        return _inf(self, batched_inputs, do_postprocess, detected_instances)          # (read under TEST.AUG.ENABLED only, where it is refused)
 
 
 WEAK_RPN_LOSSES = ["weak_loss_rpn_cls", "weak_loss_rpn_loc"]

@@ -395,6 +395,36 @@ def preprocess_images(images, pixel_mean, pixel_std, dtype=torch.bfloat16, cpad=
     return out, sizes
 
 
+def image_chw_to_u8(img):
+    """CHW fp32 (values in [0, 256), truncated toward zero) or CHW uint8 device image -> uint8 HWC: `image.permute(1, 2, 0).numpy().astype(np.uint8)`
+    of the reference's TTA (meta_arch/rcnn.py:216-218) without a stock operator"""
+    if img.dim() != 3 or img.dtype not in (torch.float32, torch.uint8):
+        raise TypeError("image_chw_to_u8 expects a CHW fp32 or uint8 image")
+    img = img.contiguous()
+    c, h, w = img.shape
+    out = torch.empty((h, w, c), dtype=torch.uint8, device=img.device)
+    check(lib().unit_image_chw_to_u8(_p(img), int(img.dtype == torch.uint8), c, h, w, _p(out), _s()), "image_chw_to_u8")
+    return out
+
+
+def tta_view_table(h, w, views):
+    """views [(new_h, new_w, flip)...] of an (h, w) image -> host float32 [V, 4] = (sx, sy, flip, W) for tta_boxes: the quotients in double,
+    rounded once, as numpy multiplies a float32 array by a python float"""
+    return torch.tensor([[new_w * 1.0 / w, new_h * 1.0 / h, float(bool(flip)), float(new_w)] for new_h, new_w, flip in views],
+                        dtype=torch.float64).to(torch.float32).reshape(-1, 4)
+
+
+def tta_boxes(props, count, views, pcap=None):
+    """props [P,4] fp32, count device int32 [1] or None, views device fp32 [V,4] (tta_view_table) -> [V,Pcap,4]: every view's proposals
+    by Detectron2's float32 apply_box + clip(min=0) rule (unit_tta_boxes); rows >= count are zeros"""
+    p = props.shape[0]
+    pcap = p if pcap is None else int(pcap)
+    v = views.shape[0]
+    out = torch.empty((v, pcap, 4), dtype=torch.float32, device=views.device)
+    check(lib().unit_tta_boxes(_p(props) if p else None, _p(count), p, pcap, _p(views), v, _p(out), _s()), "tta_boxes")
+    return out
+
+
 def nchw_to_nhwc(x, dtype=torch.bfloat16, cpad=None):
     n, c, h, w = x.shape
     cp = cpad or c
@@ -1599,6 +1629,19 @@ def softmax_rows(x, ncls):
     y = torch.empty((x.shape[0], ncls), dtype=torch.float32, device=x.device)
     check(lib().unit_softmax_rows(_p(x), x.shape[1], ncls, _p(y), ncls, x.shape[0], _s()), "softmax_rows")
     return y
+
+
+def tta_accumulate(scores, deltas, k, r, v, n, probs_sum, delta_sum, delta_mean, count=None, n_in=1, view_rows=None, scol0=0):
+    """adds the predictions of views v .. v + n_in - 1 of n (scores [.., ld] with K+1 columns from scol0, deltas [.., 4K]; R rows per view, the
+    second view `view_rows` rows behind the first) to probs_sum [R,K+1] / delta_sum [R,4K] in view order; the last view writes delta_mean =
+    delta_sum / n (unit_tta_accumulate: meta_arch/rcnn.py:516, :524)"""
+    check(lib().unit_tta_accumulate(_p(scores), scores.shape[1], scol0, _p(deltas), deltas.shape[1], r if view_rows is None else int(view_rows),
+                                    n_in, k, r, _p(count), v, n, _p(probs_sum), _p(delta_sum), _p(delta_mean), _s()), "tta_accumulate")
+
+
+def max_detection_candidates():
+    """the largest cand_cap `detections` takes: unit_nms's limit (the candidate kernel takes any cap, the sorter 2^20 keys)"""
+    return int(lib().unit_nms_max_candidates())
 
 
 def detections(probs, deltas, props, pcount, image_hw, weights, score_thresh, nms_thresh, topk, cand_cap=None):
