@@ -624,7 +624,13 @@ int unit_sgd_momentum(float* p, const float* g, float* buf, long n, float lr, fl
  * unit_sgd_step: unit_sgd_momentum on the flat range [lo, lo + n) of the buffers p, g, buf (base pointers), plus
  *   clip_mode 0: none; 1: gs = clamp(g * grad_scale, -clip_value, clip_value) (NaN stays); 2: gs = (g * grad_scale) * coefs[row of the
  *   element] (binary search over the table; elements of no row: 1), and nesterov != 0: p -= lr * (d + momentum * b) instead of lr * b.
- *   g is only read. With clip_mode 0 and nesterov 0 the result is unit_sgd_momentum's bit for bit. lr_dev as above. */
+ *   g is only read. With clip_mode 0 and nesterov 0 the result is unit_sgd_momentum's bit for bit. lr_dev as above.
+ * unit_sgd_step_masked: unit_sgd_step plus `live` (device, one byte per table row; table and n_seg > 0 are required in every clip_mode).
+ *   An element whose row has live[r] == 0 is neither read-modify-written nor stored: p and buf keep their bits whatever g holds (NaN,
+ *   stale values) -- torch.optim.SGD's treatment of a parameter whose .grad is None (no weight decay, no momentum): the weak-only
+ *   training mode (engine/defaults.py:377-400), where the RPN head and the supervised predictors never receive a gradient. Elements of
+ *   live rows and padding elements (no row) get unit_sgd_step's result bit for bit, in the vector and in the unaligned scalar form;
+ *   a vector that straddles a dead and a live row is stored element by element. A null `live` or n_seg <= 0 is an argument error. */
 int unit_grad_clip_chunk(void);
 size_t unit_grad_clip_workspace_bytes(long g_numel, int n_seg);
 int unit_grad_clip_coefs(const float* g, long g_numel, const long* table, int n_seg, int seg_lo, int seg_hi, int n_chunks, int norm_kind,
@@ -633,6 +639,9 @@ int unit_grad_clip_coefs(const float* g, long g_numel, const long* table, int n_
 int unit_sgd_step(float* p, const float* g, float* buf, long lo, long n, float lr, float momentum, float wd, float grad_scale,
                   float clip_value, int first_step, int nesterov, int clip_mode, const long* table, int n_seg, const float* coefs,
                   const float* lr_dev, void* stream);
+int unit_sgd_step_masked(float* p, const float* g, float* buf, long lo, long n, float lr, float momentum, float wd, float grad_scale,
+                         float clip_value, int first_step, int nesterov, int clip_mode, const long* table, int n_seg, const float* coefs,
+                         const unsigned char* live, const float* lr_dev, void* stream);
 
 /* ---- the step's launch sequence as a call list walked in C (csrc/replay.hip; unit_amd/_lib.py Recorder, engine.ReplayedStep) ----
  * The reference's step is `loss_dict = self.model(data, ...); losses.backward(); self.optimizer.step()` (engine/defaults.py:279-284):

@@ -4,6 +4,8 @@
 //                         rows [seg_lo, seg_hi) of a device table of (offset, numel): TWO launches for any number of tensors.
 //   unit_sgd_step         unit_sgd_momentum's update on a flat range with the clip applied on the fly (the gradient buffer is only read)
 //                         and the optional Nesterov look-ahead.
+//   unit_sgd_step_masked  unit_sgd_step that leaves the tensors of dead table rows (live[r] == 0) untouched: what torch.optim.SGD does with a
+//                         parameter whose .grad is None (no weight decay, no momentum) -- the weak-only training mode.
 //
 // Norm layout. A tensor is cut into chunks of CLIP_CHUNK elements counted from ITS OWN first element (the last one short): a chunk never
 // spans two tensors and the partition depends on the table alone. Launch 1: one 256-lane workgroup per chunk; every lane adds its
@@ -319,4 +321,120 @@ extern "C" int unit_sgd_step(float* p, const float* g, float* buf, long lo, long
   if (clip_mode == CLIP_VALUE)
     return sgd_step_launch<CLIP_VALUE>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first_step, nesterov, table, n_seg, coefs, lr_dev, st);
   return sgd_step_launch<CLIP_NONE>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first_step, nesterov, table, n_seg, coefs, lr_dev, st);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// unit_sgd_step_masked: unit_sgd_step, but an element whose table row r has live[r] == 0 is neither read-modify-written nor stored: p and
+// buf keep their bits whatever g holds. Elements of live rows and padding elements (no row) get unit_sgd_step's result bit for bit
+// (the same sgd_step_elem). A dead tensor needs no first-step flag of its own: the momentum buffer starts at zero, and
+// momentum * 0 + d == d is `first ? d : ...` on whichever step the tensor first becomes live.
+// ---------------------------------------------------------------------------------------------------
+// the table row that holds flat element idx, -1 for a padding element
+__device__ __forceinline__ int clip_row_at(const long* __restrict__ table, int n_seg, long idx) {
+  int r = clip_find_row(table, n_seg, idx);
+  return (r >= 0 && idx < table[2 * (long)r] + table[2 * (long)r + 1]) ? r : -1;
+}
+
+// same geometry as sgd_step_kernel. A workgroup inside one dead tensor returns after two wave-uniform loads (its bytes are never moved);
+// a vector inside one tensor takes that tensor's flag and coefficient; a vector that crosses a border is looked up per element, and
+// stored as a vector only when all four elements are updated -- otherwise element by element, the dead ones skipped.
+template <int MODE>
+__global__ void __launch_bounds__(256) sgd_step_masked_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long lo,
+                                                              long n, float lr, float momentum, float wd, float grad_scale, float clip_value,
+                                                              int first, int nesterov, const long* __restrict__ table, int n_seg,
+                                                              const float* __restrict__ coefs, const unsigned char* __restrict__ live,
+                                                              const float* __restrict__ lr_dev) {
+  const long e0 = (long)blockIdx.x * 1024;
+  const long i = e0 + (long)threadIdx.x * 4;
+  float cu = 1.f;
+  bool uniform = false;
+  {
+    const long b1 = lo + (e0 + 1024 < n ? e0 + 1024 : n);
+    const int r = clip_find_row(table, n_seg, lo + e0);
+    if (r >= 0 && b1 <= table[2 * (long)r] + table[2 * (long)r + 1]) {
+      if (!live[r]) return;
+      uniform = true;
+      if (MODE == CLIP_COEF) cu = coefs[r];
+    }
+  }
+  if (i >= n) return;
+  if (lr_dev) lr = lr * *lr_dev;
+  float c[4] = {cu, cu, cu, cu};
+  bool on[4] = {true, true, true, true};
+  const int cnt = i + 4 <= n ? 4 : (int)(n - i);
+  if (!uniform) {
+    const int r = clip_find_row(table, n_seg, lo + i);
+    if (r >= 0 && lo + i + cnt <= table[2 * (long)r] + table[2 * (long)r + 1]) {
+      if (!live[r]) return;
+      if (MODE == CLIP_COEF) c[0] = c[1] = c[2] = c[3] = coefs[r];
+    } else {
+      for (int j = 0; j < cnt; ++j) {
+        const int rj = clip_row_at(table, n_seg, lo + i + j);
+        on[j] = rj < 0 || live[rj] != 0;
+        if (MODE == CLIP_COEF) c[j] = rj >= 0 ? coefs[rj] : 1.f;
+      }
+    }
+  }
+  if (cnt == 4 && on[0] && on[1] && on[2] && on[3]) {
+    f32x4 pv = *reinterpret_cast<f32x4*>(p + i), gv = *reinterpret_cast<const f32x4*>(g + i);
+    f32x4 bv = *reinterpret_cast<f32x4*>(buf + i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float pj = pv[j], bj = bv[j];
+      sgd_step_elem<MODE>(pj, gv[j], bj, c[j], lr, momentum, wd, grad_scale, clip_value, first, nesterov);
+      pv[j] = pj; bv[j] = bj;
+    }
+    *reinterpret_cast<f32x4*>(p + i) = pv; *reinterpret_cast<f32x4*>(buf + i) = bv;
+  } else {
+    for (int j = 0; j < cnt; ++j)
+      if (on[j]) sgd_step_elem<MODE>(p[i + j], g[i + j], buf[i + j], c[j], lr, momentum, wd, grad_scale, clip_value, first, nesterov);
+  }
+}
+// unaligned base pointers: one element per lane
+template <int MODE>
+__global__ void __launch_bounds__(256) sgd_step_masked_scalar_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                                     long lo, long n, float lr, float momentum, float wd, float grad_scale,
+                                                                     float clip_value, int first, int nesterov, const long* __restrict__ table,
+                                                                     int n_seg, const float* __restrict__ coefs,
+                                                                     const unsigned char* __restrict__ live, const float* __restrict__ lr_dev) {
+  const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int r = clip_row_at(table, n_seg, lo + j);
+  if (r >= 0 && !live[r]) return;
+  if (lr_dev) lr = lr * *lr_dev;
+  float c = (MODE == CLIP_COEF && r >= 0) ? coefs[r] : 1.f;
+  sgd_step_elem<MODE>(p[j], g[j], buf[j], c, lr, momentum, wd, grad_scale, clip_value, first, nesterov);
+}
+
+template <int MODE>
+static int sgd_step_masked_launch(float* p, const float* g, float* buf, long lo, long n, float lr, float momentum, float wd, float grad_scale,
+                                  float clip_value, int first, int nesterov, const long* table, int n_seg, const float* coefs,
+                                  const unsigned char* live, const float* lr_dev, hipStream_t st) {
+  if (((uintptr_t)p % 16) || ((uintptr_t)g % 16) || ((uintptr_t)buf % 16))
+    sgd_step_masked_scalar_kernel<MODE><<<cdiv(n, 256), 256, 0, st>>>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first, nesterov,
+                                                                       table, n_seg, coefs, live, lr_dev);
+  else
+    sgd_step_masked_kernel<MODE><<<cdiv(n, 1024), 256, 0, st>>>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first, nesterov, table,
+                                                                n_seg, coefs, live, lr_dev);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
+extern "C" int unit_sgd_step_masked(float* p, const float* g, float* buf, long lo, long n, float lr, float momentum, float wd, float grad_scale,
+                                    float clip_value, int first_step, int nesterov, int clip_mode, const long* table, int n_seg,
+                                    const float* coefs, const unsigned char* live, const float* lr_dev, void* stream) {
+  UNIT_CHECK_ARG(live && table && (uintptr_t)table % 8 == 0, "sgd_step_masked: needs the table and one live byte per row of it");
+  UNIT_CHECK_ARG(n_seg > 0, "sgd_step_masked: n_seg must be the table's (and the mask's) row count, > 0");
+  if (n == 0) return UNIT_OK;
+  UNIT_CHECK_ARG(p && g && buf && lo >= 0 && n > 0, "sgd_step_masked: null pointer or negative range");
+  UNIT_CHECK_ARG(((uintptr_t)p % 4 == 0) && ((uintptr_t)g % 4 == 0) && ((uintptr_t)buf % 4 == 0), "sgd_step_masked: 4B alignment");
+  UNIT_CHECK_ARG(clip_mode == CLIP_NONE || clip_mode == CLIP_VALUE || clip_mode == CLIP_COEF, "sgd_step_masked: clip_mode must be 0, 1 or 2");
+  UNIT_CHECK_ARG(clip_mode != CLIP_COEF || coefs, "sgd_step_masked: coefficient mode needs coefs");
+  hipStream_t st = (hipStream_t)stream;
+  p += lo; g += lo; buf += lo;
+  if (clip_mode == CLIP_COEF)
+    return sgd_step_masked_launch<CLIP_COEF>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first_step, nesterov, table, n_seg, coefs, live, lr_dev, st);
+  if (clip_mode == CLIP_VALUE)
+    return sgd_step_masked_launch<CLIP_VALUE>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first_step, nesterov, table, n_seg, coefs, live, lr_dev, st);
+  return sgd_step_masked_launch<CLIP_NONE>(p, g, buf, lo, n, lr, momentum, wd, grad_scale, clip_value, first_step, nesterov, table, n_seg, coefs, live, lr_dev, st);
 }

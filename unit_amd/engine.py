@@ -3,6 +3,9 @@
   * TrainerNoMeta.run_step   /root/reference/engine/defaults.py:266-288 : one supervised + one weak batch per step
     (`IMS_PER_BATCH // world` images each, data/build.py:354-355), loss_dict -> sum -> backward -> optimizer.step().
   * TrainerFineTune.run_step /root/reference/engine/defaults.py:442-463 : supervised batch only.
+  * TrainerOnlyWeak.run_step /root/reference/engine/defaults.py:377-400 : weak batch only (`train_only_weak=True`); the tensors no loss
+    reaches are left untouched by the optimizer. TrainerOnlyWeakFineTune.run_step :402-425 : the classifier loader's batch as the
+    supervised batch of the default step.
 Differences by design: no per-step `comm.synchronize()` barrier (defaults.py:285), no per-step metric
 gather; losses stay on the device and are fetched only when the caller asks (`fetch_every`)."""
 
@@ -480,3 +483,68 @@ class TrainerNoMeta:
 class TrainerFineTune(TrainerNoMeta):
     def run_step(self, base_data=None, classifier_data=None):
         return super().run_step(base_data, None)
+
+
+class TrainerOnlyWeak(TrainerNoMeta):
+    """/root/reference/engine/defaults.py:377-400: the detector trains from image-level labels alone --
+    `self.model(None, weak_batched_inputs=classifier_data, train_only_weak=True)`. Both loaders are drawn from, as there (:387-388); the
+    supervised batch is dropped. The step is the model's weak-only plan (`forward_train_only_weak` / `backward_train_only_weak`); the
+    tensors no loss reaches (RPN head, delta predictors, box_head of a two-head model) receive no gradient on ANY iteration and are left
+    untouched by the optimizer (solver.MaskedFlatSGD, `unit_sgd_step_masked`), as torch.optim.SGD skips a parameter whose .grad is
+    None -- swept like an ordinary step they would decay for the whole run. Eager only."""
+
+    def __init__(self, cfg, model, data_iter=None, weak_data_iter=None, **kw):
+        from .modeling.rcnn import ONLY_WEAK_STEP_MODES
+        from .solver import MaskedFlatSGD
+        if kw.get("use_graph") or kw.get("use_replay"):
+            raise NotImplementedError(ONLY_WEAK_STEP_MODES)
+        super().__init__(cfg, model, data_iter, weak_data_iter, **kw)
+        self.optimizer = MaskedFlatSGD(model, cfg, grad_scale=self.buckets.grad_scale)
+        if self.early is not None:
+            self.early.optimizer = self.optimizer          # the per-bucket update follows the same mask
+
+    def run_step(self, base_data=None, classifier_data=None):
+        assert self.model.training, "[TrainerOnlyWeak] model was changed to eval mode!"
+        if base_data is None and self.data_iter is not None:
+            base_data = next(self.data_iter)          # drawn and dropped (:387)
+        if classifier_data is None:
+            if self.weak_data_iter is None:
+                raise ValueError("TrainerOnlyWeak.run_step: no classifier batch was given and the trainer has no weak_data_iter to draw one from")
+            classifier_data = next(self.weak_data_iter)
+        del base_data
+        model = self.model
+        step = model.forward_train_only_weak(model.pack_batch(None, classifier_data))
+        self.optimizer.set_live(model.live_entries(False, True))          # before the backward: an early per-bucket update reads it
+        model.backward_train_only_weak(step)          # every bucket is reported, the dead ones as the zeros they hold
+        self.buckets.finish()
+        if self.early is not None:
+            self.early.join()
+        self.optimizer.step()
+        self.iter += 1
+        self.last_losses = step.losses
+        return step.losses
+
+    def loss_dict(self, detect_anomaly=True):
+        """the reference's keys of this mode: loss_im_cls, loss_oicr_*, and the regression branch's two under its switch"""
+        d = super().loss_dict(detect_anomaly)
+        keep = self.model.only_weak_loss_names
+        return {k: v for k, v in d.items() if k in keep}
+
+
+class TrainerOnlyWeakFineTune(TrainerNoMeta):
+    """/root/reference/engine/defaults.py:402-425: `self.model(classifier_data, weak_batched_inputs=None)` -- the classifier loader's batch
+    as the SUPERVISED batch of an ordinary step, no weak batch; the base loader's batch is drawn (:412) and dropped"""
+
+    def run_step(self, base_data=None, classifier_data=None):
+        if base_data is None and self.data_iter is not None:
+            base_data = next(self.data_iter)
+        if classifier_data is None:
+            if self.weak_data_iter is None:
+                raise ValueError("TrainerOnlyWeakFineTune.run_step: no classifier batch was given and the trainer has no weak_data_iter to draw one from")
+            classifier_data = next(self.weak_data_iter)
+        del base_data
+        weak_iter, self.weak_data_iter = self.weak_data_iter, None          # the default step below must not draw a weak batch of its own
+        try:
+            return super().run_step(classifier_data, None)
+        finally:
+            self.weak_data_iter = weak_iter

@@ -85,7 +85,7 @@ class _StepFn(torch.autograd.Function):
         if not bool(torch.all(grad_losses[used] == 1.0)):
             raise RuntimeError("WeaklySupervisedRCNNNoMeta: backward() expects d(total)/d(loss_i) == 1 for every returned loss "
                                "(sum(loss_dict.values()).backward()); scaled / partial losses are not supported by the fused step")
-        ctx.model.backward_train(ctx.step)
+        (ctx.model.backward_train_only_weak if getattr(ctx.step, "only_weak", False) else ctx.model.backward_train)(ctx.step)
         return torch.zeros(1, device=grad_losses.device), None, None, None, None
 
 
@@ -927,22 +927,180 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
     def _sizes_on_device(self, sizes):
         return self._const_on_device(("hw", tuple(sizes)), lambda: torch.tensor(sizes, dtype=torch.float32))
 
-    def _clear_unproduced(self, c):
+    def _unfed_modules(self, has_sup, has_weak):
+        """the modules whose parameters no loss of a step reaches: a pure function of which batches the step has and of MULTI_BOX_HEAD"""
         rh, bp = self.roi_heads, self.roi_heads.box_predictor
         mods = []
-        if c.dy_weak is None:
+        if not has_weak:
             mods += list(bp.weak_detector_head.group.members)          # both streams, the refinement predictors, the regression branch
             if rh.weak_box_head is not None:
                 mods.append(rh.weak_box_head)
-        if c.dy_sup is None:
+        if not has_sup:
             mods += [bp.cls_score_delta, bp.bbox_pred_delta, self.proposal_generator.rpn_head] + \
                     ([bp.cls_score_ft, bp.bbox_pred_ft] if getattr(bp, "finetune", False) else [])
             if rh.weak_box_head is not None:
                 mods.append(rh.box_head)          # (single-head configurations: box_head also serves the weak RoIs)
-        for m in mods:
+        return mods
+
+    def _clear_unproduced(self, c):
+        for m in self._unfed_modules(c.dy_sup is not None, c.dy_weak is not None):
             for p in m.parameters():
                 if p.requires_grad and p.grad is not None:
                     p.grad.zero_()
+
+    # ------------------------------------------------------------------ the weak-only step (train_only_weak=True, TrainerOnlyWeak)
+    # A plan of its own beside forward_train / backward_train, which stay as they are: the reference's meta_arch/rcnn.py:437-491 with
+    # batched_inputs=None is a short chain -- backbone (with gradient), RPN forward-only, first-k RoIs, RoIAlign, one Res5 head, the weak
+    # detector's fused losses -- and none of the default plan's forks (RPN branch, two head chains, supervised losses) exists in it.
+    only_weak_refused = None          # a meta-architecture that cannot take the mode says why (WeaklySupervisedRCNNRPN)
+
+    def live_entries(self, has_sup, has_weak):
+        """one bool per TRAINABLE entry of the flat store, in `store.entries` order (the rows of solver.clip_table): does a step with /
+        without a supervised and a weak batch produce a gradient for it? False = torch leaves the parameter's .grad at None and
+        torch.optim.SGD skips it. The same module lists `_clear_unproduced` zeroes; frozen stages have no entry at all."""
+        if self.store is None or not self.store.is_current():
+            self.flatten_parameters()
+        dead = {id(p) for m in self._unfed_modules(has_sup, has_weak) for p in m.parameters()}
+        return tuple(id(e["param"]) not in dead for e in self.store.entries if e["param"].requires_grad)
+
+    def only_weak_tag_sequence(self):
+        """the gradient buckets in the order the weak-only backward reports them: the ones a loss reaches as they become final (the order of
+        `store.tags`), then the dead ones -- every tag once, whatever the mode, so a data-parallel rank never waits for a bucket that was
+        not announced"""
+        live = self.live_entries(False, True)
+        ents = [e for e in self.store.entries if e["param"].requires_grad]
+        fed = {}
+        for tag, a, b in self.store.tags:
+            fed[tag] = fed.get(tag, False) or any(l and a <= e["offset"] < b for l, e in zip(live, ents))
+        return [t for t in fed if fed[t]] + [t for t in fed if not fed[t]]
+
+    @property
+    def only_weak_loss_names(self):
+        """the keys of the mode's dictionary (rcnn.py:466-467, fast_rcnn.py `losses(..., train_only_weak=True)`): no RPN losses, no
+        supervised losses -- the weak head's alone"""
+        sup = ("loss_cls", "loss_box_reg", "loss_rpn_cls", "loss_rpn_loc", "loss_mask")
+        return [n for n in self.loss_names if n not in sup]
+
+    def _check_only_weak(self, batch):
+        """train_only_weak=True: what the reference's own code cannot run in this mode is refused with the line that stops it"""
+        from .inference import UnsupportedConfig
+        from .roi_heads import WSROIHeadNoMetaWithMask
+        rh = self.roi_heads
+        if self.only_weak_refused:
+            raise NotImplementedError(self.only_weak_refused)
+        if batch.n_sup > 0:
+            raise NotImplementedError(ONLY_WEAK_WITH_SUPERVISED)
+        if batch.n_weak == 0:
+            raise ValueError("train_only_weak=True needs weak_batched_inputs (roi_heads.py:526: the box predictor would be called on None, None)")
+        if isinstance(rh, WSROIHeadNoMetaWithMask):          # (and its fine-tune subclass)
+            raise UnsupportedConfig(ONLY_WEAK_MASK_HEAD.format(type(rh).__name__))
+        if getattr(rh, "finetune", False):
+            raise UnsupportedConfig(ONLY_WEAK_FINETUNE.format(type(rh).__name__))
+        if self._x3:
+            raise NotImplementedError(ONLY_WEAK_X3)
+
+    def forward_train_only_weak(self, batch):
+        """-> step context of a batch of weak images alone (`losses` on the device, everything backward_train_only_weak needs). No sampling
+        permutation is drawn, no anchor or RoI is labelled, nothing of the RPN head is saved for a backward (rcnn.py:468-470: no_grad)."""
+        self._check_only_weak(batch)
+        self._ensure_ready()
+        if self.plan is not None:
+            self.plan.begin_step()
+        rpn, rh, wh = self.proposal_generator, self.roi_heads, self.roi_heads.box_predictor.weak_detector_head
+        dt = self.compute_dtype
+        c = type("StepCtx", (), {})()
+        c.n_sup, c.n_weak, c.only_weak, c.split, c.mask_ctx = 0, batch.n_weak, True, False, None
+        c.losses = ops.zeros(len(self.loss_names), torch.float32, self.device)
+        c.metrics = ops.zeros(step_metrics.SIZE, torch.int32, self.device) if self.collect_metrics else None
+        self.last_metrics, self.last_metrics_images = c.metrics, 0          # (no supervised image: no rpn/*, roi_head/*, fast_rcnn/* scalar)
+        x, sizes = ops.preprocess_images(batch.images, self._pixel_mean, self._pixel_std, dt, 8, self.normalize_images)
+        feat, c.bb_ctx = self.backbone.fwd(x, save=True, before_trainable=self.join_optimizer_tail)          # with gradient (:452)
+        self.join_optimizer_tail()
+        c.image_sizes = sizes
+        c.feat = ops.as_f32(feat)
+        _, fh, fw, _ = c.feat.shape
+        head, _ = rpn.rpn_head.fwd(feat, save=False)
+        c.proposals = props, _, pcount = rpn.predict_proposals(head, rpn.anchor_generator.grid(fh, fw), self._sizes_on_device(sizes), True)
+        sw = rh.batch_size_per_image // rh.weak_divisor          # roi_heads.py:566-572: the first proposals of every image
+        c.rs, c.rw = 0, batch.n_weak * sw
+        c.rois, c.weak_valid = rh.weak_rois(props, pcount, 0)
+        pooled = rh.pool(c.feat, c.rois)
+        c.head = rh.weak_box_head if rh.weak_box_head is not None else rh.box_head          # :512-515
+        c.weak_feat, c.head_ctx = c.head.fwd(pooled, save=True)
+        lin = wh.group.fwd(c.weak_feat)
+        reg_kw = dict(reg_loss_out=c.losses[len(LOSS_NAMES):]) if wh.regression_branch else {}
+        c.dy_weak = wh.fused_losses(lin, c.rois, c.weak_valid, sw, batch.n_weak, batch.multihot, c.losses[2:6], dt,
+                                    side_stream=self._rpn_stream if self._streams_on() else None, **reg_kw)
+        return c
+
+    def backward_train_only_weak(self, c):
+        """the weak head's predictors, its Res5 head, RoIAlign and the backbone in reverse; the ranges no loss reaches are cleared by the
+        library's own fill and EVERY gradient bucket is reported final -- the fed ones as they complete, then the dead ones, which travel
+        as the zeros they hold: the data-parallel schedule does not depend on the mode"""
+        rh, wh = self.roi_heads, self.roi_heads.box_predictor.weak_detector_head
+        self._reattach_grads()
+        hook, plan, final = self.on_grad_ready, self.plan, self.on_bucket_final
+        side = self._wgrad_stream if self._streams_on() else None
+        ops.WGRAD_STREAM = side if plan is not None else None
+        announced = set()
+
+        def done(tag):          # (backward_train's bucket boundary: slab reduction and the hooks on the weight-gradient stream)
+            announced.add(tag)
+            if side is not None:
+                if hook is not None or final is not None:
+                    side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    plan.reduce(tag)
+                    if hook is not None:
+                        hook(tag)
+                if final is not None:
+                    final(tag, side)
+                return
+            if plan is not None:
+                plan.reduce(tag)
+            if hook is not None:
+                hook(tag)
+
+        # every iteration of a run clears the same tensors: their flat ranges, merged, by the library's fill (no stock operator in the step)
+        st = self.store
+        merged, prev_dead = [], False
+        for l, e in zip(self.live_entries(False, True), (e for e in st.entries if e["param"].requires_grad)):
+            if not l:
+                if prev_dead:          # (what lies between two neighbouring dead tensors is padding: cleared with them)
+                    merged[-1][1] = e["offset"] + e["numel"]
+                else:
+                    merged.append([e["offset"], e["offset"] + e["numel"]])
+            prev_dead = not l
+        for a, b in merged:
+            ops.zero_(st.grads[a:b])
+        dweak = wh.group.bwd(c.weak_feat, c.dy_weak, need_dx=True)
+        done("heads")
+        dpool = c.head.bwd(c.head_ctx, dweak)
+        done("weak_box_head" if c.head is rh.weak_box_head else "box_head")
+        if self.backbone.first_trainable_stage() < 3:
+            g = torch.empty_like(c.feat)
+            rh.pool_bwd_gather(ops.as_f32(dpool), c.n_weak, c.feat.shape[1], c.feat.shape[2], c.rois, g, image_offset=0, mask_ref=c.feat)
+            self.backbone.bwd(c.bb_ctx, g, on_stage_done=done)
+        for tag in dict.fromkeys(t for t, _, _ in st.tags):
+            if tag not in announced:
+                done(tag)
+        if side is not None:
+            if self.overlap_optimizer_tail and not torch.cuda.is_current_stream_capturing():
+                side.wait_stream(torch.cuda.current_stream())
+                self._tail_pending = side
+            else:
+                torch.cuda.current_stream().wait_stream(side)
+        ops.WGRAD_STREAM = None
+
+    def train_step_only_weak(self, batch, optimizer=None):
+        """forward + backward (+ a solver.MaskedFlatSGD update) of the weak-only step without torch.autograd; -> the device loss vector"""
+        step = self.forward_train_only_weak(batch)
+        if optimizer is not None:
+            optimizer.set_live(self.live_entries(False, True))          # before the backward: an early per-bucket update reads it
+        self.backward_train_only_weak(step)
+        if optimizer is not None:
+            optimizer.step()
+        return step.losses
 
     def _streams_on(self):
         """HIP-stream overlap (independent Res5 heads, weight-gradient kernels) -- on by default on the GPU."""
@@ -988,9 +1146,15 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         perms, self.next_perms = getattr(self, "next_perms", None), None
         if not self.training:
             return self.inference(batched_inputs, return_similarity=return_similarity)
-        if train_only_weak:
-            raise NotImplementedError("train_only_weak is not used by TrainerNoMeta / TrainerFineTune (engine/defaults.py:279,454)")
         batch = batched_inputs if isinstance(batched_inputs, PackedBatch) else self.pack_batch(batched_inputs, weak_batched_inputs)
+        if train_only_weak:          # rcnn.py:433 with batched_inputs=None (TrainerOnlyWeak, engine/defaults.py:391): the weak-only plan
+            step = self.forward_train_only_weak(batch)
+            if self._anchor is None or self._anchor.device != self.device:
+                self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
+            all_names, names = self.loss_names, self.only_weak_loss_names
+            used = torch.tensor([n in names for n in all_names], device=self.device)
+            lv = _StepFn.apply(self._anchor, self, step, step.losses, used)
+            return {n: lv[all_names.index(n)] for n in names}
         step = self.forward_train(batch, perms)
         if self._anchor is None or self._anchor.device != self.device:
             self._anchor = torch.zeros(1, device=self.device, requires_grad=True)
@@ -1019,6 +1183,25 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         self.join_optimizer_tail()
         return _inf(self, batched_inputs, do_postprocess, detected_instances)          # (read under TEST.AUG.ENABLED only, where it is refused)
 
+
+ONLY_WEAK_WITH_SUPERVISED = (
+    "train_only_weak=True with supervised images is not supported: in the reference only the ROI heads read the flag (roi_heads.py:497, :560 "
+    "skip the supervised RoIs) while the RPN still trains on the supervised images (meta_arch/rcnn.py:463-464); the fused plan has no step "
+    "with an RPN branch but without supervised RoIs. TrainerOnlyWeak (engine/defaults.py:391) passes batched_inputs=None")
+ONLY_WEAK_MASK_HEAD = (
+    "train_only_weak=True is not supported with {}: the reference calls _forward_mask(None, None, box_features=None) "
+    "(roi_heads.py:813), which has no supervised proposals to select foreground RoIs from")
+ONLY_WEAK_FINETUNE = (
+    "train_only_weak=True is not supported with {}: its _forward_box calls get_similarity_matrices(None) (roi_heads.py:618) on the "
+    "supervised box features the mode does not compute")
+ONLY_WEAK_X3 = ("train_only_weak=True: compute_mode \"bf16x3\" has not been taken through a step without supervised images; use \"bf16\" or "
+                "\"fp32\"")
+ONLY_WEAK_RPN_CLASS = (
+    "WeaklySupervisedRCNNRPN does not take train_only_weak: its forward preprocesses batched_inputs unconditionally "
+    "(meta_arch/rcnn.py:550) and cannot take None")
+ONLY_WEAK_STEP_MODES = (
+    "TrainerOnlyWeak runs eagerly only: engine.GraphedStep / ReplayedStep do not take the weak-only step yet (its optimizer update is the "
+    "masked kernel, whose mask is not part of a batch key). Use use_graph=False, use_replay=False")
 
 WEAK_RPN_LOSSES = ["weak_loss_rpn_cls", "weak_loss_rpn_loc"]
 
@@ -1050,6 +1233,7 @@ class WeaklySupervisedRCNNRPN(WeaklySupervisedRCNNNoMeta):
     the sum. Same state-dict keys, same inference as WeaklySupervisedRCNNNoMeta."""
 
     step_modes_refused = STEP_MODES_REFUSED
+    only_weak_refused = ONLY_WEAK_RPN_CLASS
 
     def __init__(self, cfg, thing_classes=None):
         from .inference import UnsupportedConfig

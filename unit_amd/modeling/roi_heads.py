@@ -140,8 +140,18 @@ class WSROIHeadNoMeta(nn.Module):
         if self.training:
             # roi_heads.py:553-591 in training under a meta-architecture other than the fused step: ONE autograd node over the heads'
             # explicit forward / backward (modeling/train_modules.py) -> (sampled proposals, {loss_cls, loss_box_reg, loss_im_cls, loss_oicr_*})
-            if tta or return_similarity or return_proposals or train_only_weak:
-                raise NotImplementedError("tta / return_similarity / return_proposals / train_only_weak are outside the hot path (SURVEY.md section 2)")
+            if tta or return_similarity or return_proposals:
+                raise NotImplementedError("tta / return_similarity / return_proposals are outside the hot path (SURVEY.md section 2)")
+            if train_only_weak:
+                # roi_heads.py:560-577 with train_only_weak=True: no sampling, the weak RoIs alone -> (None, the weak head's losses)
+                from .inference import UnsupportedConfig
+                from .rcnn import ONLY_WEAK_FINETUNE, ONLY_WEAK_WITH_SUPERVISED
+                if getattr(self, "finetune", False):
+                    raise UnsupportedConfig(ONLY_WEAK_FINETUNE.format(type(self).__name__))
+                if features is not None or proposals is not None:
+                    raise NotImplementedError(ONLY_WEAK_WITH_SUPERVISED)
+                from .train_modules import roi_heads_forward_train_only_weak
+                return None, roi_heads_forward_train_only_weak(self, weak_features, weak_proposals, weak_targets)
             from .train_modules import roi_heads_forward_train
             return roi_heads_forward_train(self, features, proposals, targets, weak_features, weak_proposals, weak_targets)
         if tta or return_similarity or return_proposals:
@@ -260,8 +270,12 @@ class WSROIHeadNoMetaWithMask(WSROIHeadNoMeta):
         if self.training:
             # roi_heads.py:783-822 / :909-952 in training under a meta-architecture other than the fused step: one autograd node over the
             # heads' explicit forward / backward incl. the mask head on the foreground RoIs (modeling/train_modules.py)
-            if tta or return_similarity or train_only_weak:
-                raise NotImplementedError("tta / return_similarity / train_only_weak are outside the hot path (SURVEY.md section 2)")
+            if tta or return_similarity:
+                raise NotImplementedError("tta / return_similarity are outside the hot path (SURVEY.md section 2)")
+            if train_only_weak:
+                from .inference import UnsupportedConfig
+                from .rcnn import ONLY_WEAK_MASK_HEAD
+                raise UnsupportedConfig(ONLY_WEAK_MASK_HEAD.format(type(self).__name__))
             from .train_modules import roi_heads_forward_train
             return roi_heads_forward_train(self, features, proposals, targets, weak_features, weak_proposals, weak_targets)
         if tta or return_similarity:

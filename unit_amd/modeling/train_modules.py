@@ -377,6 +377,67 @@ def roi_heads_forward_train(rh, features, proposals, targets, weak_features, wea
     return sampled, {n: lv[all_names.index(n)] for n in names}
 
 
+class _WeakHeadsFn(torch.autograd.Function):
+    """WSROIHeadNoMeta in training with train_only_weak=True (roi_heads.py:497-515 with `features` None): the weak RoIs alone -- RoIAlign,
+    weak_box_head (box_head without MULTI_BOX_HEAD), the weak predictors and their fused losses -- as one node; the segments of the fused
+    weak-only step (rcnn.forward_train on a batch without supervised images)."""
+
+    @staticmethod
+    def forward(ctx, fw, rh, io):
+        from .inference import pack_proposal_instances
+        dtype = _dtype(rh)
+        rh.prepare(dtype, _pversion(rh))
+        wh = rh.box_predictor.weak_detector_head
+        feat_w = ops.as_f32(_nhwc(fw, dtype))
+        dev = feat_w.device
+        n_weak = feat_w.shape[0]
+        sw = rh.batch_size_per_image // rh.weak_divisor
+        wprops, wcount = pack_proposal_instances(io["weak_proposals"], dev)
+        rois, weak_valid = rh.weak_rois(wprops, wcount, 0)
+        pooled = rh.pool(feat_w, rois)
+        head = rh.weak_box_head if rh.weak_box_head is not None else rh.box_head
+        wfeat, hctx = head.fwd(pooled, save=True)
+        lin = wh.group.fwd(wfeat)
+        losses = ops.zeros(wh.n_losses, torch.float32, dev)
+        multihot = torch.zeros((n_weak, rh.num_classes), dtype=torch.uint8)
+        for i, c in enumerate(io["weak_targets"]):
+            multihot[i, c.long().cpu()] = 1          # torch.unique(gt_classes) (weak_detector_fast_rcnn.py:203)
+        reg_kw = dict(reg_loss_out=losses[1 + wh.oicr_iter:]) if wh.regression_branch else {}
+        dy = wh.fused_losses(lin, rois, weak_valid, sw, n_weak, multihot.to(dev), losses[:1 + wh.oicr_iter], dtype, **reg_kw)
+        ctx.rh, ctx.head, ctx.saved = rh, head, (wfeat, hctx, dy, rois, feat_w.shape, n_weak)
+        return losses
+
+    @staticmethod
+    def backward(ctx, gl):
+        rh, head = ctx.rh, ctx.head
+        wfeat, hctx, dy, rois, fwshape, n_weak = ctx.saved
+        _check_unit_weights(gl, type(rh).__name__)
+        with _direct_grads():
+            dweak = rh.box_predictor.weak_detector_head.group.bwd(wfeat, dy, need_dx=True)
+            dpool = head.bwd(hctx, dweak)
+        gw = torch.empty(fwshape, dtype=torch.float32, device=rois.device)
+        rh.pool_bwd_gather(ops.as_f32(dpool), n_weak, fwshape[1], fwshape[2], rois, gw)
+        return ops.nhwc_to_nchw(gw), None, None
+
+
+def roi_heads_forward_train_only_weak(rh, weak_features, weak_proposals, weak_targets):
+    """-> {loss_im_cls, loss_oicr_1..n[, loss_regression_cls, loss_regression_bbox]} with an autograd graph into `weak_features`"""
+    assert weak_features is not None and weak_proposals is not None and weak_targets is not None, \
+        "train_only_weak=True needs weak_features, weak_proposals and weak_targets (roi_heads.py:509, :526)"
+    fw = weak_features["res4"] if isinstance(weak_features, dict) else weak_features
+    if not fw.requires_grad:          # (a fully frozen backbone: the node stays part of the graph for its parameters' sake)
+        fw = fw + _anchor(rh, fw.device) * 0
+    io = {"weak_proposals": weak_proposals, "weak_targets": weak_targets}
+    lv = _WeakHeadsFn.apply(fw, rh, io)
+    wh = rh.box_predictor.weak_detector_head
+    names = ["loss_im_cls"] + [f"loss_oicr_{i + 1}" for i in range(wh.oicr_iter)]
+    if wh.regression_branch:
+        from .fast_rcnn import REGRESSION_LOSSES
+        names = names + REGRESSION_LOSSES
+    rh._last_train_io = io
+    return {n: lv[i] for i, n in enumerate(names)}
+
+
 # ------------------------------------------------------------------------------------------------ predictors on their own
 # SupervisedDetectorOutputs{Base,FineTune}.forward / .losses (fast_rcnn.py:384-453, :484-533) and WeakDetectorOutputsBase.forward / .losses
 # (weak_detector_fast_rcnn.py:148-255) in TRAINING mode, for a caller that composes the predictors itself: the predictions and the losses

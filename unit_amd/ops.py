@@ -448,6 +448,13 @@ def zeros(shape, dtype, device):
     return t
 
 
+def zero_(t):
+    """t.zero_() for a contiguous tensor by the library's own fill kernel"""
+    assert t.is_contiguous()
+    check(lib().unit_fill_zero(_p(t), t.numel() * t.element_size(), _s()), "fill_zero")
+    return t
+
+
 def cast(x, dtype):
     y = torch.empty(x.shape, dtype=dtype, device=x.device)
     check(lib().unit_cast(_p(x.contiguous()), dt(x.dtype), _p(y), dt(dtype), x.numel(), _s()), "cast")
@@ -1822,6 +1829,25 @@ def sgd_step(p, g, buf, lo, n, lr, momentum, weight_decay, grad_scale=1.0, first
     check(lib().unit_sgd_step(_p(p), _p(g), _p(buf), int(lo), int(n), float(lr), float(momentum), float(weight_decay), float(grad_scale),
                               float(clip_value), int(first_step), int(bool(nesterov)), int(clip_mode), _p(table),
                               0 if table is None else table.shape[0], _p(coefs), _p(lr_dev), _s()), "sgd_step")
+
+
+def sgd_step_masked(p, g, buf, lo, n, lr, momentum, weight_decay, table, live, grad_scale=1.0, first_step=False, lr_dev=None, nesterov=False,
+                    clip_mode=CLIP_NONE, clip_value=0.0, coefs=None):
+    """sgd_step that leaves the tensors of dead rows untouched: `live` uint8 [table rows] on the device, 0 = p and buf of that row keep
+    their bits whatever g holds (torch.optim.SGD on a parameter whose .grad is None). Live rows and padding: sgd_step's result bit for bit.
+    The table is needed in every clip_mode."""
+    assert p.dtype == g.dtype == buf.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous() and buf.is_contiguous()
+    assert 0 <= lo and lo + n <= min(p.numel(), g.numel(), buf.numel())
+    assert table is not None and table.dtype == torch.int64 and table.is_contiguous() and table.dim() == 2
+    if live is not None:
+        assert live.dtype == torch.uint8 and live.is_contiguous()
+        if live.numel() != table.shape[0]:
+            raise ValueError(f"sgd_step_masked: {live.numel()} live flags for a table of {table.shape[0]} rows")
+    if clip_mode == CLIP_COEF:
+        assert coefs.dtype == torch.float32 and coefs.numel() >= table.shape[0]
+    check(lib().unit_sgd_step_masked(_p(p), _p(g), _p(buf), int(lo), int(n), float(lr), float(momentum), float(weight_decay), float(grad_scale),
+                                     float(clip_value), int(first_step), int(bool(nesterov)), int(clip_mode), _p(table), table.shape[0],
+                                     _p(coefs), _p(live), _p(lr_dev), _s()), "sgd_step_masked")
 
 
 # ------------------------------------------------------------------------------------------------ training metrics (csrc/metrics.hip)

@@ -233,3 +233,58 @@ class FlatSGD:
         self._first = False
         self.iter += 1
         self.model.after_optimizer_step()
+
+
+class MaskedFlatSGD(FlatSGD):
+    """FlatSGD for the weak-only mode (engine.TrainerOnlyWeak, `train_only_weak=True`): torch leaves the .grad of a parameter no loss reaches
+    at None and torch.optim.SGD skips it -- no weight decay, no momentum. FlatSGD sweeps the whole flat buffer, so a cleared range still
+    decays; harmless for an occasional step without one batch, but in this mode the same tensors (RPN head, delta predictors, box_head of a
+    two-head model) go without a gradient on EVERY iteration. Here the caller names, before every step, the trainable entries that received
+    a gradient (`set_live(model.live_entries(...))`), and `unit_sgd_step_masked` neither read-modify-writes nor stores an element of a dead
+    row; live rows and padding get `unit_sgd_step`'s result bit for bit. FlatSGD itself is untouched: a step that merely lacks one batch
+    keeps its cleared, swept ranges.
+    Dead rows need no first-step flag of their own: the momentum buffer starts at zero, so momentum * 0 + d == d is torch's buf = clone(d)
+    on whichever step a tensor first becomes live. Under "norm" / "full_model" clipping the dead rows' gradients are the zeros the step
+    cleared: their norms add nothing. `step_tag` (EarlyUpdate) and `step` go through the same `_apply`, so both follow the mask. The mask
+    belongs to ONE step: `step()` consumes it, an update without one is an error, and so is a store that was re-flattened in between."""
+
+    def __init__(self, model, cfg, lr_schedule=None, grad_scale=1.0):
+        super().__init__(model, cfg, lr_schedule=lr_schedule, grad_scale=grad_scale)
+        self._live = None         # tuple of bools, one per table row, for the step about to be applied; None = not set
+        self._live_dev = self._live_store = self._mask_table = None
+
+    def set_live(self, live):
+        """live: one bool per trainable entry of the store (`clip_table` order), True = the step produced a gradient for it"""
+        st = self._bind()
+        live = tuple(bool(x) for x in live)
+        if len(live) != len(self.names):
+            raise ValueError(f"set_live: {len(live)} flags for the {len(self.names)} trainable tensors of the store")
+        if self._mask_table is None or self._live_store is not st:
+            rows = [(o, e - o) for o, e in zip(self._row_off, self._row_end)]
+            self._mask_table = self._table if self._table is not None else torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(st.params.device)
+        self._live, self._live_store = live, st
+        # uploaded once per distinct mask (no host-to-device copy inside a step after the first of a kind)
+        self._live_dev = self.model._const_on_device(("sgd_live", id(st), live), lambda: torch.tensor(live, dtype=torch.uint8))
+
+    def _apply(self, st, lo, hi):
+        if self._live is None:
+            raise RuntimeError("MaskedFlatSGD: set_live() names the tensors with a gradient before every step (model.live_entries)")
+        if self._live_store is not st:
+            raise RuntimeError("MaskedFlatSGD: the parameter store was re-flattened after set_live(); the mask belongs to the old store")
+        lr = self.schedule(self.iter) if self._lr_dev is None else 1.0
+        mode, value = self._clip_mode, (self.clip[1] if self.clip else 0.0)
+        if mode == ops.CLIP_COEF:
+            r0, r1 = self._rows_in(lo, hi)
+            if r0 < r1:
+                ops.grad_clip_coefs(st.grads, self._table, r0, r1, self._chunk_prefix[r1] - self._chunk_prefix[r0], self.clip[2], value,
+                                    self.grad_scale, self._norms, self._coefs, self._clip_ws, full_model=self.clip[0] == "full_model")
+        for off, n, (lr_mult, wd) in self._segments:
+            a, b = max(off, lo), min(off + n, hi)
+            if a < b:
+                ops.sgd_step_masked(st.params, st.grads, self._buf, a, b - a, lr * lr_mult, self.momentum, wd, self._mask_table, self._live_dev,
+                                    self.grad_scale, first_step=self._first, lr_dev=self._lr_dev, nesterov=self.nesterov, clip_mode=mode,
+                                    clip_value=value, coefs=self._coefs)
+
+    def _step(self):
+        super()._step()
+        self._live = self._live_dev = None          # consumed: the next step names its own
