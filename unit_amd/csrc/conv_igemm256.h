@@ -31,7 +31,8 @@ __device__ __forceinline__ int swz256(int row, int chunk) { return row * 128 + (
 
 typedef __attribute__((address_space(3))) void lds_void;
 
-// conv_igemm256p8.hip: the 8-phase (4 per k-tile) schedule of the same tile
-int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st);
+// conv_igemm256p8.hip: the 8-phase (4 per k-tile) schedule of the same tile. loop: how the load sections issue their LDS-DMA pieces (template
+// parameter SCHED there): 1 = the production loop, 0 = the first loop (variant 13 of unit_conv2d_fwd_big / _ex / _pair: A/B runs, bit-identity tests)
+int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st, int loop = 1);
 // conv_igemm256p8m.hip: the same schedule on v_mfma_f32_32x32x16_bf16 (256-row tiles)
 int unit_conv256_p8m_launch(Conv256Args& a, int out_dtype, hipStream_t st);

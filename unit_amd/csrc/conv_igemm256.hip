@@ -616,8 +616,8 @@ int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias,
   hipStream_t st = (hipStream_t)stream;
   if (variant == 0) variant = 8;          // the production kernel; everything below decodes an explicit variant
   if (a.second.on) {          // pair launch: the phase-interleaved kernel on row-major 256-row tiles
-    UNIT_CHECK_ARG(out_dtype == UNIT_BF16 && (ldy & 7) == 0 && (variant == 8 || variant == 12), "conv_big: pair launches: bf16 output, ldy % 8 == 0, variant 0 / 8 / 12");
-    return unit_conv256_p8_launch(a, out_dtype, true, false, st);
+    UNIT_CHECK_ARG(out_dtype == UNIT_BF16 && (ldy & 7) == 0 && (variant == 8 || variant == 12 || variant == 13), "conv_big: pair launches: bf16 output, ldy % 8 == 0, variant 0 / 8 / 12");
+    return unit_conv256_p8_launch(a, out_dtype, true, false, st, variant == 13 ? 0 : 1);
   }
   // 224 or 256 rows per tile, whichever needs fewer rounds x rows (variants 5 and 10; isolated launches gain 5-7 % on the Res5 shapes:
   // 50 176 = 224 * 224 pixels; inside the multi-stream step the other streams already fill the partial last round and the 7 % extra
@@ -638,6 +638,9 @@ int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias,
   if (variant == 11) return unit_conv256_p8m_launch(a, out_dtype, st);
   // 12: variant 8 with row-major tiles even where position-major tiles apply (A/B and bit-identity tests)
   if (variant == 12) return unit_conv256_p8_launch(a, out_dtype, true, false, st);
+  // 13: variant 8 (position-class tiles included) with the first loop of the kernel (conv_igemm256p8.hip SCHED 0; A/B and bit-identity tests)
+  int loop = 1;
+  if (variant == 13) { variant = 8; loop = 0; }
   // 7 / 8: four phases per k-tile, half-tile staging under a counted vmcnt; 8 also issues the fragment reads inside the MFMA sections
   // (conv_igemm256p8.hip). 9: variant 8 on 224-row tiles; 10: 224 or 256 rows per launch
   if (variant >= 7 && variant <= 10) {
@@ -645,7 +648,7 @@ int unit_conv_big_impl(const void* x, const void* w, void* y, const float* bias,
     // position-class tiles (Conv256Args::pm_ncls): 3x3 s1 p1 conv on a small map, plain bf16 output, when skipping the all-padding
     // taps saves more k-tiles than padding every class to whole tiles costs
     if (variant == 8 && out_dtype == UNIT_BF16 && (ldy & 7) == 0 && conv_position_classes_apply(a, 2)) build_position_classes(a);
-    return unit_conv256_p8_launch(a, out_dtype, variant >= 8, r224, st);
+    return unit_conv256_p8_launch(a, out_dtype, variant >= 8, r224, st, loop);
   }
   // the two-stage kernels. 4 (and any other number): one barrier per k-tile, 256-row tiles; 3: 224-row tiles; 5: 224 or 256 rows per launch;
   // 1: ping-pong wave groups; 2: four 32-k stages
@@ -759,7 +762,7 @@ extern "C" int unit_conv2d_fwd_big_ex(const void* x, const void* w, void* y, con
                                       const unsigned char* mask_bits, unsigned char* relu_bits, float* pool_partial, int pool_rows,
                                       int N, int H, int W, int C, int K, int R, int S, int pad, int ldy, int relu, const void* x2, int C2,
                                       int variant, void* stream) {
-  UNIT_CHECK_ARG(variant == 0 || variant == 8 || variant == 11, "conv_big_ex: variant 0 (default), 8 (16x16x32 MFMA) or 11 (32x32x16 MFMA)");
+  UNIT_CHECK_ARG(variant == 0 || variant == 8 || variant == 11 || variant == 13, "conv_big_ex: variant 0 (default), 8 (16x16x32 MFMA) or 11 (32x32x16 MFMA)");
   // x2 != NULL: 1x1 conv over the channel concatenation [x (C channels) | x2 (C2 channels)] of two tensors of the same N, H, W;
   // w = [K][C + C2]. C2 must be a multiple of C.
   UNIT_CHECK_ARG(x2 == nullptr || (R == 1 && S == 1 && pad == 0 && C2 > 0 && C2 % C == 0 && ((uintptr_t)x2 % 16 == 0)),
@@ -781,7 +784,7 @@ extern "C" int unit_conv2d_fwd_big_ex(const void* x, const void* w, void* y, con
   a.ex = EpiExtra{relu_bits, mask_bits, pool_partial, pool_rows}; a.ex_on = 1;
   if (a.M == 0 || K == 0) return UNIT_OK;
   if (variant == 11) return unit_conv256_p8m_launch(a, UNIT_BF16, (hipStream_t)stream);
-  return unit_conv256_p8_launch(a, UNIT_BF16, true, false, (hipStream_t)stream);
+  return unit_conv256_p8_launch(a, UNIT_BF16, true, false, (hipStream_t)stream, variant == 13 ? 0 : 1);
 }
 
 // pooled[r][n] = (1 / rows) * sum of the partial sums of RoI r: its rows [r*rows, (r+1)*rows) lie in at most two 128-row wave tiles

@@ -44,8 +44,48 @@ extern "C" int unit_debug_read_stamps(unsigned long long* host_out) {
   return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * 32 * 16, 0, hipMemcpyDeviceToHost);
 }
 #define P8_STAMP(i) do { if (stamp) stamp[(i)] = __builtin_amdgcn_s_memtime(); } while (0)
+// the main loop of the RM schedule (tools/p8_loop_stamp.sh): waves 0 and 4 (one per wave group) of every 29th workgroup stamp s_memtime in the
+// middle k-tile of their (first) tile -- [0] top of the k-tile, [1 + i] behind its i-th barrier (load section, MFMA section, ... of phases
+// 0-3; each interval includes the wait at the barrier that closes it) -- and at [9] loop entry, [10] loop exit; [13] = k-tiles, [14] =
+// blockIdx.x, [15] = wave. Kept in scalar registers (low 32 bits: only differences are read) until the loop is over -- a store inside the
+// loop would join the counted vmcnt queue -- then written by lane 0 with plain vector stores.
+__device__ unsigned long long g_loop_stamp[64 * 16];
+extern "C" int unit_debug_read_loop_stamps(unsigned long long* host_out) {
+  return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_loop_stamp), sizeof(unsigned long long) * 64 * 16, 0, hipMemcpyDeviceToHost);
+}
+// (one asm statement: the wait keeps the stamp's own return off the lgkmcnt counts of the section behind it; every stamp sits behind a barrier
+//  in front of which the wave's fragment reads were already retired)
+#define P8_LOOP_STAMP_INIT()                                                                              \
+  unsigned ts[11];                                                                                        \
+  _Pragma("unroll") for (int i = 0; i < 11; ++i) ts[i] = 0;                                               \
+  const bool lstamp_on = (wid & 3) == 0 && blockIdx.x % 29 == 0 && blockIdx.x / 29 < 32;                  \
+  const int lstamp_t = nk >> 1
+#define P8_LOOP_STAMP_IF(c, i)                                                                            \
+  do {                                                                                                    \
+    if (lstamp_on && (c)) {                                                                               \
+      unsigned long long t64;                                                                             \
+      __builtin_amdgcn_sched_barrier(0);                                                                  \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t64) :: "memory");                       \
+      __builtin_amdgcn_sched_barrier(0);                                                                  \
+      ts[(i)] = (unsigned)t64;                                                                            \
+    }                                                                                                     \
+  } while (0)
+#define P8_LOOP_STAMP(i) P8_LOOP_STAMP_IF(true, i)
+#define P8_LOOP_STAMP_T(i) P8_LOOP_STAMP_IF(t == lstamp_t, i)
+#define P8_LOOP_STAMP_OUT(first)                                                                          \
+  do {                                                                                                    \
+    if (lstamp_on && (first) && lane == 0) {                                                              \
+      unsigned long long* g = g_loop_stamp + ((blockIdx.x / 29) * 2 + (wid >> 2)) * 16;                   \
+      _Pragma("unroll") for (int i = 0; i < 11; ++i) g[i] = ts[i];                                        \
+      g[13] = (unsigned long long)nk; g[14] = blockIdx.x; g[15] = (unsigned long long)wid;                \
+    }                                                                                                     \
+  } while (0)
 #else
 #define P8_STAMP(i) do { } while (0)
+#define P8_LOOP_STAMP_INIT() do { } while (0)
+#define P8_LOOP_STAMP(i) do { } while (0)
+#define P8_LOOP_STAMP_T(i) do { } while (0)
+#define P8_LOOP_STAMP_OUT(first) do { } while (0)
 #endif
 
 #define MFMA_BF16(A, B, C) __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, A), __builtin_bit_cast(bf16x8, B), C, 0, 0, 0)
@@ -60,8 +100,20 @@ extern "C" int unit_debug_read_stamps(unsigned long long* host_out) {
 // PERS (round 5): one workgroup per CU walks the row-major tiles bid, bid + gridDim.x, ... and issues the first k-tiles of its NEXT tile before the
 // epilogue of the current one, whose scratch moves behind the operand slots that prologue fills (LDS 146 KB): the 4.7 k cycles between a workgroup's
 // start and its first MFMA -- 12 % of a K = 512 tile, profiles/r05_exp_epilogue_diet.txt -- run under the epilogue's 7.8 k instead of after it.
-template <typename TO, bool RM, int B1, bool X3 = false, bool PAIR = false, bool PERS = false>
+// SCHED (RM schedule, bf16 rows, 256-row tiles; profiles/r13_fwd_loop.txt): how a load section issues its two LDS-DMA pieces.
+//   0  the first form, kept for A/B runs and as the reference of tests/test_fwd_loop_gpu.py (variant 13 of unit_conv2d_fwd_big): per piece a
+//      wave-uniform branch on "second input?", the k-tile's byte offset added and the bounds folded in on the VALU.
+//   1  (default of the plain, position-class and PAIR launches) lean issue: the k-tile's byte offset of a W piece goes through the
+//      instruction's scalar offset, so the piece is {m0, buffer_load ... lds} with no VALU and no branch (a channel past K keeps the
+//      out-of-range marker as its vector offset, which is what the range check sees); an X piece adds on the VALU as before (a tap left of or
+//      above the map wraps its vector offset) but without a branch: the input a k-tile reads is chosen once per k-tile with the offsets, by
+//      scalar selects. Same sources, same LDS image, same order of pieces under the same counted vmcnt: 3.46 k -> 2.97 k stamped cycles per
+//      k-tile on the Res5 3x3, isolated launches 5 - 8 % faster. The PERS launches keep SCHED 0: their pieces never had the tap tests, and
+//      the lean form measured 1 - 2 % SLOWER there (and two / one pieces hoisted into the wave's preceding MFMA section 3 - 17 % slower
+//      everywhere) -- profiles/r13_fwd_loop.txt.
+template <typename TO, bool RM, int B1, bool X3 = false, bool PAIR = false, bool PERS = false, int SCHED = 0>
 __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p) {
+  static_assert(SCHED == 0 || (RM && B1 == 4 && !X3 && !PERS && sizeof(TO) == 2), "SCHED 1: 256-row RM schedule, bf16 rows, plain operands, one tile per workgroup");
   static_assert(RM || B1 == 4, "224-row tiles: RM schedule only");
   static_assert(!PAIR || (RM && B1 == 4), "pair launches: 256-row RM schedule");
   static_assert(!X3 || (RM && sizeof(TO) == 2), "bf16x3 operands: RM schedule, split bf16 output");
@@ -192,10 +244,13 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
   int st_sg = 0, st_cbr = 0;            // X3: segment of the virtual channel block st_cb, and the real 64-channel block it reads (st_cb = st_cbr * nseg + st_sg)
   unsigned st_kx = (unsigned)((st_r * p.W + st_s) * Cx) * 2u, st_kw = (unsigned)((st_r * p.S + st_s) * p.C) * 2u;
   if constexpr (X3) st_kx += (unsigned)((p.sk.seg_lo & 1) * p.sk.cr) * 2u;
+  // SCHED 1: whether the k-tile reads the second input (then st_kx is its byte offset inside a row of x2) -- decided here, once per k-tile
+  bool st_x2 = false;
   auto st_reset = [&]() {               // back to the first k-tile (PERS: the next tile of this workgroup)
     st_cb = 0; st_r = r_lo; st_s = s_lo; st_sg = 0; st_cbr = 0;
     st_kx = (unsigned)((st_r * p.W + st_s) * Cx) * 2u; st_kw = (unsigned)((st_r * p.S + st_s) * p.C) * 2u;
     if constexpr (X3) st_kx += (unsigned)((p.sk.seg_lo & 1) * p.sk.cr) * 2u;
+    st_x2 = false;                      // (cb_split >= 1)
   };
   auto st_advance = [&]() {
     if (++st_s > s_hi) {
@@ -208,8 +263,35 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
     if constexpr (X3) st_kx = (unsigned)((st_r * p.W + st_s) * Cx + ((p.sk.seg_lo >> st_sg) & 1) * p.sk.cr + st_cbr * BK) * 2u;
     else st_kx = (unsigned)((st_r * p.W + st_s) * Cx + st_cb * BK) * 2u;
     st_kw = (unsigned)((st_r * p.S + st_s) * p.C + st_cb * BK) * 2u;
+    if constexpr (SCHED != 0) {
+      st_x2 = dual && st_cb >= p.cb_split;
+      if (st_x2) st_kx = (unsigned)((st_cb - p.cb_split) * BK) * 2u;
+    }
+  };
+  // SCHED 1: vector offset of X piece i = q * 2 + j in the current k-tile
+  auto x_voff = [&](int i) -> unsigned {
+    unsigned v = x_off0[i];
+    int ih = x_ih0[i] + st_r, iw = x_iw0[i] + st_s;
+    bool ok = (unsigned)ih < (unsigned)p.H && (unsigned)iw < (unsigned)p.W;
+    if (st_x2) v = (v - sw16) * (unsigned)p.ratio2 + sw16;      // the row of x2: same pixel, ratio2 times the pitch; the swizzle term stays
+    return ok ? v + st_kx : OOB;
+  };
+  auto issue_x = [&](int q, int d, int j, unsigned voff) {
+    lds_void* dst = (lds_void*)(smem + d * BUF + (q ? SX1 : SX0) + (j * 8 + wid) * 1024);
+    // (the descriptor of the input this k-tile reads: scalar selects of its base and size)
+    __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(st_x2 ? (const bf16_t*)p.x2 : X), 0, (int)(st_x2 ? p.x2_bytes : p.x_bytes), 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst, 16, voff, 0, 0, 0);
+  };
+  auto issue_w = [&](int q, int d, int j) {
+    lds_void* dst = (lds_void*)(smem + d * BUF + (q ? SW1 : SW0) + (j * 8 + wid) * 1024);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, dst, 16, w_off[q * 2 + j], st_kw, 0, 0);
   };
   auto stage_x = [&](int q, int d) {
+    if constexpr (SCHED != 0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) issue_x(q, d, j, x_voff(q * 2 + j));
+      return;
+    }
     char* base = smem + d * BUF + (q ? SX1 : SX0);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -227,6 +309,11 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
     }
   };
   auto stage_w = [&](int q, int d) {
+    if constexpr (SCHED != 0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) issue_w(q, d, j);
+      return;
+    }
     char* base = smem + d * BUF + (q ? SW1 : SW0);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -372,6 +459,7 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
       st_advance();
       if (nk > 1) { stage_x(0, 1); stage_w(0, 1); stage_w(1, 1); }
     };
+    P8_LOOP_STAMP_INIT();
     prologue_stage();
     if (nk > 1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -383,22 +471,24 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
     read_x(smem + SX0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     if (grp == 1) P8_BAR();
+    P8_LOOP_STAMP(9);
     for (int t = 0; t < nk; ++t) {
       const int d = t & 1;
       const char* buf = smem + d * BUF;
       const char* bnx = smem + (d ^ 1) * BUF;
       const bool n1 = t + 1 < nk, n2 = t + 2 < nk;
+      P8_LOOP_STAMP_T(0);
       // phase 0
       if (n1) stage_x(1, d ^ 1);
       st_advance();
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(1);
       P8_MM(0, 0, fw0, fx, 4, 4, 1, read_w(buf + SW1, fw1));
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(2);
       // phase 1
       if (n2) stage_x(0, d);
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(3);
       P8_MM(0, 1, fw1, fx, 4, 2 * B1, RD_PER, read_xb(buf + SX1));
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(4);
       // phase 2
       if (n2) {
         stage_w(0, d);
@@ -406,15 +496,17 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(5);
       P8_MM(1, 0, fw0, fxb, B1, 0, 1, (void)0);
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(6);
       // phase 3 (after the last k-tile the reads fetch stale, in-bounds LDS that nobody uses)
       if (n2) stage_w(1, d);
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(7);
       P8_MM(1, 1, fw1, fxb, B1, 12, RD_PER, read_w(bnx + SW0, fw0); read_x(bnx + SX0));
-      P8_BAR();
+      P8_BAR(); P8_LOOP_STAMP_T(8);
     }
+    P8_LOOP_STAMP(10);
+    P8_LOOP_STAMP_OUT(pers_v == (int)blockIdx.x);
     if (grp == 0) P8_BAR();
     if constexpr (!PERS) break;
     else {
@@ -560,13 +652,24 @@ __global__ void __launch_bounds__(512, 2) conv_igemm256_p8_kernel(Conv256Args p)
   }
 }
 
+// the loop schedules a launcher instantiates: the first one everywhere; SCHED 1 where it is defined (256-row RM schedule, bf16 rows, plain operands, not PERS)
+#define P8_BY_SCHED(F)                                                                                      \
+  do {                                                                                                      \
+    if constexpr (RM && B1 == 4 && !X3 && sizeof(TO) == 2) {                                                \
+      if (loop == 1) return F(1);                               \
+    }                                                                                                       \
+    return F(0);                                                                                            \
+  } while (0)
+
 template <typename TO, bool RM, int B1, bool X3 = false>
-static int launch256_p8(Conv256Args& a, hipStream_t st) {
+static int launch256_p8(Conv256Args& a, hipStream_t st, int loop) {
   if (a.second.on) {          // pair launch (conv_epilogue.h ConvSecond): row-major 256-row tiles of both problems in one grid
     if constexpr (RM && B1 == 4 && sizeof(TO) == 2) {
       a.pm_ncls = 0;
       a.tiles_m = cdiv(a.M, 256); a.tiles_n = cdiv(a.K, 256);
-      return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, true>>(pair_grid(a, 256), 512, 8 * 128 * 128, a, st);
+#define P8_F(S) conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, true, false, S>>(pair_grid(a, 256), 512, 8 * 128 * 128, a, st)
+      P8_BY_SCHED(P8_F);
+#undef P8_F
     } else {
       unit_set_error("conv_big: pair launches need the 256-row RM schedule with bf16 output");
       return UNIT_ERR_UNSUPPORTED;
@@ -602,20 +705,23 @@ static int launch256_p8(Conv256Args& a, hipStream_t st) {
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8) n = 256;
         ncu = n / 8 * 8;
       }
-      return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, false, true>>(grid < ncu ? grid : ncu, 512, lds_p, a, st);
+      return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, false, true>>(grid < ncu ? grid : ncu, 512, lds_p, a, st);          // (SCHED 0 only)
     }
   }
-  return conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3>>(grid, 512, lds, a, st);
+#define P8_F(S) conv_launch<conv_igemm256_p8_kernel<TO, RM, B1, X3, false, false, S>>(grid, 512, lds, a, st)
+  P8_BY_SCHED(P8_F);
+#undef P8_F
 }
 
-int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st) {
+// loop: the template parameter SCHED of the kernels that have two loops (0 = the first loop, 1 = the default); every other kernel runs its only loop
+int unit_conv256_p8_launch(Conv256Args& a, int out_dtype, bool reads_in_mfma, bool rows224, hipStream_t st, int loop) {
   if (a.sk.nseg > 1) {             // bf16x3 operands (unit_conv2d_fwd_x3)
     if (out_dtype != UNIT_BF16 || (a.ldy & 7) != 0 || rows224 || !reads_in_mfma) { unit_set_error("conv_big: bf16x3 operands need the 256-row RM schedule and split output rows of 16-byte vectors"); return UNIT_ERR_UNSUPPORTED; }
-    return launch256_p8<bf16_t, true, 4, true>(a, st);          // (a pair launch goes through the same launcher)
+    return launch256_p8<bf16_t, true, 4, true>(a, st, loop);          // (a pair launch goes through the same launcher)
   }
   if (rows224 && !reads_in_mfma) { unit_set_error("conv_big: 224-row tiles need the reads-in-MFMA schedule"); return UNIT_ERR_UNSUPPORTED; }
-  if (out_dtype == UNIT_BF16) return rows224 ? launch256_p8<bf16_t, true, 3>(a, st) : reads_in_mfma ? launch256_p8<bf16_t, true, 4>(a, st) : launch256_p8<bf16_t, false, 4>(a, st);
-  if (out_dtype == UNIT_F32) return rows224 ? launch256_p8<float, true, 3>(a, st) : reads_in_mfma ? launch256_p8<float, true, 4>(a, st) : launch256_p8<float, false, 4>(a, st);
+  if (out_dtype == UNIT_BF16) return rows224 ? launch256_p8<bf16_t, true, 3>(a, st, loop) : reads_in_mfma ? launch256_p8<bf16_t, true, 4>(a, st, loop) : launch256_p8<bf16_t, false, 4>(a, st, loop);
+  if (out_dtype == UNIT_F32) return rows224 ? launch256_p8<float, true, 3>(a, st, loop) : reads_in_mfma ? launch256_p8<float, true, 4>(a, st, loop) : launch256_p8<float, false, 4>(a, st, loop);
   unit_set_error("conv_big: unsupported out dtype");
   return UNIT_ERR_UNSUPPORTED;
 }

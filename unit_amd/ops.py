@@ -290,6 +290,7 @@ TILE_CFG = {
     20: ("mid", 5),      # 4-wave 96 x 128, two LDS stages
     21: ("big", 11),     # the schedule of 8 on v_mfma_f32_32x32x16_bf16
     22: ("big", 12),     # 8 without the position-class tiles
+    23: ("big/first-loop", 13),     # 8 with the kernel's first main loop (conv_igemm256p8.hip SCHED 0): the A/B partner of the production loop
 }
 
 # side HIP stream for the weight-gradient kernels (set by the model when stream overlap is enabled; None = inline)
@@ -531,7 +532,7 @@ def conv2d(x, w, k, r, s, stride=1, pad=0, bias=None, residual=None, mask_ref=No
         mid = tile_cfg
     elif tile_cfg in TILE_CFG:
         kind, code = TILE_CFG[tile_cfg]
-        if kind == "big":
+        if kind.startswith("big"):
             big, variant = True, code
         else:
             mid = code
