@@ -352,6 +352,23 @@ int unit_roi_align_bwd_gather(const void* gout, int dtype, int N, int H, int W, 
                               const void* mask_ref, void* dfeat, int out_dtype, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---- a8 RoIPool (MODEL.ROI_BOX_HEAD.POOLER_TYPE "ROIPool"): roi_heads.py:499,511 via detectron2 ROIPooler -> torchvision.ops.RoIPool ----
+ * Max over integer windows of the feature grid (corners roundf'ed, halves away from zero; first maximum in row-major order, NaN never
+ * selected); out [R, out_size, out_size, C] holds the selected elements bit for bit, +0 for an empty bin. pooled_size / out_size /
+ * bin_step, roi_count_dev and the batch-index rule are unit_roi_align_fwd's. argmax: NULL (inference, nothing stored) or int32
+ * [R, out_size, out_size, C] = y * W + x inside the RoI's image, -1 for none (unit_roi_pool_argmax_bytes of it). */
+size_t unit_roi_pool_argmax_bytes(int R, int out_size, int C);
+int unit_roi_pool_fwd(const void* feat_nhwc, int dtype, int N, int H, int W, int C, const float* rois, const int* roi_count_dev, int R,
+                      int pooled_size, int out_size, int bin_step, float spatial_scale, void* out, void* argmax, void* stream);
+
+/* deterministic gather-form backward from the forward's argmax (no atomics, additions only, RoIs in ascending slot order and bins row-major);
+ * the other arguments and the fused "+ addend, * (mask_ref > 0), cast" epilogue are unit_roi_align_bwd_gather's */
+size_t unit_roi_pool_bwd_gather_workspace_bytes(int R);
+int unit_roi_pool_bwd_gather(const void* gout, const void* argmax, int dtype, int N, int H, int W, int C, const float* rois,
+                             const int* roi_count_dev, int R, int rois_per_image, int image_offset, int pooled_size, int out_size,
+                             int bin_step, float spatial_scale, const void* addend, int addend_images, const void* mask_ref, void* dfeat,
+                             int out_dtype, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- a5/a10/a11/a12 fused loss forward+backward kernels ---- */
 /* scratch (unit_rpn_loss_scratch_bytes, contents irrelevant): per-workgroup partial sums, added by the last workgroup in a fixed
  * order -- the two loss scalars are bit-reproducible */

@@ -68,6 +68,11 @@ def pack_gt_masks(ms, dev, mcap):
     return gt_masks.to(dev, non_blocking=True)
 
 
+def _rows(t, lo, hi):
+    """t[lo:hi] of an optional per-RoI tensor (ROIPool's argmax buffer: None under the RoIAlign pooler types)"""
+    return None if t is None else t[lo:hi]
+
+
 class _StepFn(torch.autograd.Function):
     """Exposes the explicit plan to torch.autograd as one node: forward has already run, backward runs the backward plan."""
 
@@ -504,13 +509,15 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         if n_weak > 0:
             _, c.weak_valid = rh.weak_rois(props[n_sup:], pcount[n_sup:], n_sup, rois_out=c.rois[rs:])
         c.rs, c.rw = rs, rw
-        if not split:
-            pooled = rh.pool(feat, c.rois)
+        if not split:          # (c.pool_argmax: POOLER_TYPE "ROIPool" leaves its selection beside `pooled` for the gather backward; else None)
+            pooled, c.pool_argmax = rh.pool_train(feat, c.rois)
         else:   # two feature tensors, one pooled buffer: supervised RoIs from `feat`, weak RoIs (batch index rebased) from `feat_w`
             osz = rh.pool_out[0]
             pooled = torch.empty((rs + rw, osz, osz, fc), dtype=feat.dtype, device=feat.device)
-            rh.pool(feat, c.rois[:rs], out=pooled[:rs])
-            rh.pool(feat_w, c.rois[rs:], out=pooled[rs:], image_offset=n_sup)          # (the RoIs' batch indices count from the supervised images)
+            c.pool_argmax = rh.new_argmax(pooled)
+            rh.pool(feat, c.rois[:rs], out=pooled[:rs], argmax=_rows(c.pool_argmax, 0, rs))
+            rh.pool(feat_w, c.rois[rs:], out=pooled[rs:], image_offset=n_sup,          # (the RoIs' batch indices count from the supervised images)
+                    argmax=_rows(c.pool_argmax, rs, rs + rw))
 
         # a9 Res5 heads: box_head on the supervised RoIs (grad); weak_box_head on ALL RoIs in one pass -- its supervised
         # half is the reference's no_grad evaluation (roi_heads.py:502-504), its weak half has grad (:512-513)
@@ -817,7 +824,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
             def grad_map(ft, dp, n_im, r_lo, r_hi, img0, add, out=None):
                 out = out if out is not None else torch.empty_like(ft)
                 if dp is not None:
-                    rh.pool_bwd_gather(dp, n_im, ft.shape[1], ft.shape[2], c.rois[r_lo:r_hi], out, image_offset=img0, addend=add, mask_ref=ft)
+                    rh.pool_bwd_gather(dp, n_im, ft.shape[1], ft.shape[2], c.rois[r_lo:r_hi], out, image_offset=img0, addend=add, mask_ref=ft,
+                                       argmax=_rows(c.pool_argmax, r_lo, r_hi))
                 else:
                     ops.add_cast(ops.zeros(ft.shape, torch.float32, ft.device), add, dt, mask_ref=ft, out=out)
                 return out
@@ -830,7 +838,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
                         continue
                     if dp is not None:
                         rh.pool_bwd_gather(dp, hi - lo, fh, fw, c.rois[r_lo:r_hi], g[lo:hi], image_offset=lo, addend=add,
-                                           mask_ref=feat[lo:hi])
+                                           mask_ref=feat[lo:hi], argmax=_rows(c.pool_argmax, r_lo, r_hi))
                     else:
                         z = ops.zeros(feat[lo:hi].shape, torch.float32, feat.device)
                         ops.add_cast(z, add, dt, mask_ref=feat[lo:hi], out=g[lo:hi])
@@ -1024,7 +1032,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         sw = rh.batch_size_per_image // rh.weak_divisor          # roi_heads.py:566-572: the first proposals of every image
         c.rs, c.rw = 0, batch.n_weak * sw
         c.rois, c.weak_valid = rh.weak_rois(props, pcount, 0)
-        pooled = rh.pool(c.feat, c.rois)
+        pooled, c.pool_argmax = rh.pool_train(c.feat, c.rois)
         c.head = rh.weak_box_head if rh.weak_box_head is not None else rh.box_head          # :512-515
         c.weak_feat, c.head_ctx = c.head.fwd(pooled, save=True)
         lin = wh.group.fwd(c.weak_feat)
@@ -1079,7 +1087,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         done("weak_box_head" if c.head is rh.weak_box_head else "box_head")
         if self.backbone.first_trainable_stage() < 3:
             g = torch.empty_like(c.feat)
-            rh.pool_bwd_gather(ops.as_f32(dpool), c.n_weak, c.feat.shape[1], c.feat.shape[2], c.rois, g, image_offset=0, mask_ref=c.feat)
+            rh.pool_bwd_gather(ops.as_f32(dpool), c.n_weak, c.feat.shape[1], c.feat.shape[2], c.rois, g, image_offset=0, mask_ref=c.feat,
+                               argmax=c.pool_argmax)
             self.backbone.bwd(c.bb_ctx, g, on_stage_done=done)
         for tag in dict.fromkeys(t for t, _, _ in st.tags):
             if tag not in announced:

@@ -33,6 +33,9 @@ def coco_indexer(thing_classes):
     return [idx[_VOC2COCO.get(n, n)] for n in thing_classes]
 
 
+POOLER_TYPES = ("ROIAlignV2", "ROIAlign", "ROIPool")
+
+
 @ROI_HEADS_REGISTRY.register()
 class WSROIHeadNoMeta(nn.Module):
     finetune = False
@@ -48,7 +51,12 @@ class WSROIHeadNoMeta(nn.Module):
         self.pooler_resolution = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
         self.pooler_scale = 1.0 / 16
         self.sampling_ratio = cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO
-        assert cfg.MODEL.ROI_BOX_HEAD.POOLER_TYPE == "ROIAlignV2"
+        # Detectron2's ROIPooler types: "ROIAlignV2" (aligned), "ROIAlign" (legacy, aligned=False), "ROIPool" (csrc/roi_pool.hip: max, no
+        # sampling ratio); "ROIAlignRotated" needs 5-parameter boxes this project does not carry
+        self.pooler_type = cfg.MODEL.ROI_BOX_HEAD.POOLER_TYPE
+        if self.pooler_type not in POOLER_TYPES:
+            from .inference import UnsupportedConfig
+            raise UnsupportedConfig(f"MODEL.ROI_BOX_HEAD.POOLER_TYPE = {self.pooler_type!r}: supported are {', '.join(POOLER_TYPES)}")
         self.mask_on = cfg.MODEL.MASK_ON
         self.pool_mode = "strided"   # "full": materialise all 14x14 bins like the reference (parity tests)
         in_ch = input_shape["res4"].channels if input_shape else 1024
@@ -119,16 +127,45 @@ class WSROIHeadNoMeta(nn.Module):
     def weak_rois(self, props, pcount, batch_index_offset, rois_out=None):
         return ops.first_k_rois(props, pcount, self.batch_size_per_image // self.weak_divisor, batch_index_offset, rois_out=rois_out)
 
-    def pool(self, feat, rois5, out=None, image_offset=0):
+    @property
+    def max_pool(self):
+        return self.pooler_type == "ROIPool"
+
+    def new_argmax(self, pooled):
+        """the buffer RoIPool's forward leaves its selection in for the backward, beside `pooled` [R, out, out, C]; None for the RoIAlign types"""
+        return torch.empty(pooled.shape, dtype=torch.int32, device=pooled.device) if self.max_pool else None
+
+    def pool_train(self, feat, rois5):
+        """pool() for a step that runs a backward: -> (pooled, the argmax buffer pool_bwd_gather wants back -- None unless ROIPool)"""
+        if not self.max_pool:
+            return self.pool(feat, rois5), None
+        osz = self.pool_out[0]
+        pooled = torch.empty((rois5.shape[0], osz, osz, feat.shape[3]), dtype=feat.dtype, device=feat.device)
+        argmax = self.new_argmax(pooled)
+        return self.pool(feat, rois5, out=pooled, argmax=argmax), argmax
+
+    def pool(self, feat, rois5, out=None, image_offset=0, argmax=None):
+        """argmax: ROIPool in training -- int32 like the output (new_argmax), filled for pool_bwd / pool_bwd_gather; None: nothing is stored"""
         osz, step = self.pool_out
-        return ops.roi_align(feat, rois5, self.pooler_resolution, osz, step, self.pooler_scale, self.sampling_ratio, True, out=out,
-                             image_offset=image_offset)
+        if self.max_pool:
+            return ops.roi_pool(feat, rois5, self.pooler_resolution, osz, step, self.pooler_scale, out=out, argmax=argmax,
+                                image_offset=image_offset)
+        return ops.roi_align(feat, rois5, self.pooler_resolution, osz, step, self.pooler_scale, self.sampling_ratio,
+                             self.pooler_type == "ROIAlignV2", out=out, image_offset=image_offset)
 
-    def pool_bwd(self, dpooled, feat_shape, rois5, dfeat32):
+    def pool_bwd(self, dpooled, feat_shape, rois5, dfeat32, argmax=None):
         _, step = self.pool_out
+        if self.max_pool:          # no scatter kernel: the gather with the accumulator as its addend (dfeat32 = gather + dfeat32, in place per element)
+            n, h, w, c = feat_shape
+            if dfeat32 is None:
+                dfeat32 = ops.zeros((n, h, w, c), torch.float32, dpooled.device)
+            dpooled = ops.as_f32(dpooled)
+            if dpooled.dtype != torch.float32:          # (the addend is read in the gradient's type)
+                dpooled = ops.cast(dpooled, torch.float32)
+            return ops.roi_pool_bwd_gather(dpooled, argmax, n, h, w, rois5, dfeat32, self.pooler_resolution, step, self.pooler_scale,
+                                           addend=dfeat32, addend_images=n)
         return ops.roi_align_bwd(dpooled, feat_shape, rois5, dfeat32, self.pooler_resolution, step, self.pooler_scale,
-                                 self.sampling_ratio, True)
-
+                                 self.sampling_ratio, self.pooler_type == "ROIAlignV2")
 
     # ---- plugin surface: the reference's signature (roi_heads.py:553). Eval executes the HIP path; training is the fused step.
     def forward(self, images, features, proposals, targets=None, weak_images=None, weak_features=None, weak_proposals=None,
@@ -223,12 +260,18 @@ class WSROIHeadNoMeta(nn.Module):
             o += c
         return instances
 
-    def pool_bwd_gather(self, dpooled, n_images, h, w, rois5, out, image_offset=0, addend=None, mask_ref=None):
-        """deterministic gather-form RoIAlign backward fused with '+ RPN-branch gradient, * ReLU mask' (fixed RoI slots)."""
+    def pool_bwd_gather(self, dpooled, n_images, h, w, rois5, out, image_offset=0, addend=None, mask_ref=None, argmax=None):
+        """deterministic gather-form pooler backward fused with '+ RPN-branch gradient, * ReLU mask' (fixed RoI slots).
+        argmax: ROIPool only -- the rows of the forward's argmax buffer that belong to `rois5`."""
         _, step = self.pool_out
         s = rois5.shape[0] // n_images
+        if self.max_pool:
+            return ops.roi_pool_bwd_gather(dpooled, argmax, n_images, h, w, rois5, out, self.pooler_resolution, step, self.pooler_scale,
+                                           rois_per_image=s if s * n_images == rois5.shape[0] else 0, image_offset=image_offset,
+                                           addend=addend, addend_images=n_images if addend is not None else 0, mask_ref=mask_ref)
         return ops.roi_align_bwd_gather(dpooled, n_images, h, w, rois5, out, self.pooler_resolution, step, self.pooler_scale,
-                                        self.sampling_ratio, True, rois_per_image=s if s * n_images == rois5.shape[0] else 0,
+                                        self.sampling_ratio, self.pooler_type == "ROIAlignV2",
+                                        rois_per_image=s if s * n_images == rois5.shape[0] else 0,
                                         image_offset=image_offset, addend=addend, addend_images=n_images if addend is not None else 0,
                                         mask_ref=mask_ref)
 

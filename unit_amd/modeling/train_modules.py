@@ -216,9 +216,10 @@ class _HeadsFn(torch.autograd.Function):
             _, weak_valid = rh.weak_rois(wprops, wcount, n_sup, rois_out=rois[rs:])
         osz = rh.pool_out[0]
         pooled = torch.empty((rs + rw, osz, osz, feat.shape[3]), dtype=feat.dtype, device=dev)
-        rh.pool(feat, rois[:rs], out=pooled[:rs])
+        argmax = rh.new_argmax(pooled)          # POOLER_TYPE "ROIPool": the selection the gather backward reads; None otherwise
+        rh.pool(feat, rois[:rs], out=pooled[:rs], argmax=None if argmax is None else argmax[:rs])
         if has_weak:
-            rh.pool(feat_w, rois[rs:], out=pooled[rs:], image_offset=n_sup)
+            rh.pool(feat_w, rois[rs:], out=pooled[rs:], image_offset=n_sup, argmax=None if argmax is None else argmax[rs:])
         multi = rh.weak_box_head is not None
         mh = getattr(rh, "mask_head", None)
         ft = bool(getattr(bp, "finetune", False))
@@ -236,7 +237,7 @@ class _HeadsFn(torch.autograd.Function):
         lin_sup = bp.group.fwd(box_feat)
         lin_weak = wh.group.fwd(wfeat_all)
         losses = ops.zeros(len(HEAD_LOSSES) + (2 if wh.regression_branch else 0), torch.float32, dev)
-        st = {"mask_ctx": None, "dsim_mask": None, "sel": None}
+        st = {"mask_ctx": None, "dsim_mask": None, "sel": None, "pool_argmax": argmax}
 
         def run_mask(sim=None, roles=None):          # rcnn.forward_train run_mask (roi_heads.py:691-710 / :888-906)
             from .mask_head import gather_match_index, mask_targets, mask_targets_polygon
@@ -340,13 +341,14 @@ class _HeadsFn(torch.autograd.Function):
                 dpool_sup, dpool_weak = dpool[:rs], (dpool[rs:] if rw > 0 else None)
             else:
                 dpool_sup = dpool_weak = None
-        dev = rois.device
+        dev, argmax = rois.device, st["pool_argmax"]
         if dpool_sup is not None:
             g = torch.empty(fshape, dtype=torch.float32, device=dev)
-            rh.pool_bwd_gather(ops.as_f32(dpool_sup), n_sup, fshape[1], fshape[2], rois[:rs], g)
+            rh.pool_bwd_gather(ops.as_f32(dpool_sup), n_sup, fshape[1], fshape[2], rois[:rs], g, argmax=None if argmax is None else argmax[:rs])
         if dpool_weak is not None:
             gw = torch.empty(fwshape, dtype=torch.float32, device=dev)
-            rh.pool_bwd_gather(ops.as_f32(dpool_weak), n_weak, fwshape[1], fwshape[2], rois[rs:], gw, image_offset=n_sup)
+            rh.pool_bwd_gather(ops.as_f32(dpool_weak), n_weak, fwshape[1], fwshape[2], rois[rs:], gw, image_offset=n_sup,
+                               argmax=None if argmax is None else argmax[rs:])
         return (ops.nhwc_to_nchw(g) if g is not None else None), (ops.nhwc_to_nchw(gw) if gw is not None else None), None, None
 
 
@@ -394,7 +396,7 @@ class _WeakHeadsFn(torch.autograd.Function):
         sw = rh.batch_size_per_image // rh.weak_divisor
         wprops, wcount = pack_proposal_instances(io["weak_proposals"], dev)
         rois, weak_valid = rh.weak_rois(wprops, wcount, 0)
-        pooled = rh.pool(feat_w, rois)
+        pooled, argmax = rh.pool_train(feat_w, rois)
         head = rh.weak_box_head if rh.weak_box_head is not None else rh.box_head
         wfeat, hctx = head.fwd(pooled, save=True)
         lin = wh.group.fwd(wfeat)
@@ -404,19 +406,19 @@ class _WeakHeadsFn(torch.autograd.Function):
             multihot[i, c.long().cpu()] = 1          # torch.unique(gt_classes) (weak_detector_fast_rcnn.py:203)
         reg_kw = dict(reg_loss_out=losses[1 + wh.oicr_iter:]) if wh.regression_branch else {}
         dy = wh.fused_losses(lin, rois, weak_valid, sw, n_weak, multihot.to(dev), losses[:1 + wh.oicr_iter], dtype, **reg_kw)
-        ctx.rh, ctx.head, ctx.saved = rh, head, (wfeat, hctx, dy, rois, feat_w.shape, n_weak)
+        ctx.rh, ctx.head, ctx.saved = rh, head, (wfeat, hctx, dy, rois, feat_w.shape, n_weak, argmax)
         return losses
 
     @staticmethod
     def backward(ctx, gl):
         rh, head = ctx.rh, ctx.head
-        wfeat, hctx, dy, rois, fwshape, n_weak = ctx.saved
+        wfeat, hctx, dy, rois, fwshape, n_weak, argmax = ctx.saved
         _check_unit_weights(gl, type(rh).__name__)
         with _direct_grads():
             dweak = rh.box_predictor.weak_detector_head.group.bwd(wfeat, dy, need_dx=True)
             dpool = head.bwd(hctx, dweak)
         gw = torch.empty(fwshape, dtype=torch.float32, device=rois.device)
-        rh.pool_bwd_gather(ops.as_f32(dpool), n_weak, fwshape[1], fwshape[2], rois, gw)
+        rh.pool_bwd_gather(ops.as_f32(dpool), n_weak, fwshape[1], fwshape[2], rois, gw, argmax=argmax)
         return ops.nhwc_to_nchw(gw), None, None
 
 

@@ -1338,6 +1338,52 @@ def roi_align_bwd_gather(gout, n_images, h, w, rois, out, pooled_size=14, bin_st
     return out
 
 
+def roi_pool(feat, rois, pooled_size=14, out_size=None, bin_step=1, spatial_scale=1.0 / 16, roi_count=None, out=None, argmax=None,
+             image_offset=0):
+    """torchvision's RoIPool (csrc/roi_pool.hip) with roi_align's out_size / bin_step / image_offset. argmax: None (nothing stored) or an
+    int32 tensor shaped like the output, filled with y * W + x inside the RoI's image (-1: none) -- image-local under `image_offset` too, so
+    that roi_pool_bwd_gather on the same slice of the batch reads what this call wrote."""
+    n, h, w, c = feat.shape
+    r = rois.shape[0]
+    out_size = out_size or pooled_size
+    if out is None:
+        out = torch.empty((r, out_size, out_size, c), dtype=feat.dtype, device=feat.device)
+    assert out.shape == (r, out_size, out_size, c) and out.dtype == feat.dtype and out.is_contiguous() and feat.is_contiguous()
+    if argmax is not None:
+        assert argmax.shape == out.shape and argmax.dtype == torch.int32 and argmax.is_contiguous()
+        assert argmax.numel() * 4 == lib().unit_roi_pool_argmax_bytes(r, out_size, c)
+    es = feat.element_size()
+    nb_arg = 0 if argmax is None else argmax.numel() * 4
+    # algorithmic bytes as roi_align's: the maps once + the pooled tensor (+ its argmax) once; `ref` = the full pooled_size x pooled_size grid
+    with _timed("roi_pool_fwd", 0.0, (feat.numel() + r * out_size * out_size * c) * es + nb_arg,
+                (feat.numel() + r * pooled_size * pooled_size * c) * es + (nb_arg // (out_size * out_size)) * pooled_size * pooled_size):
+        _p(feat)
+        base = ctypes.c_void_p(feat.data_ptr() - image_offset * h * w * c * es)
+        check(lib().unit_roi_pool_fwd(base, dt(feat.dtype), n + image_offset, h, w, c, _p(rois), _p(roi_count), r, pooled_size, out_size, bin_step,
+                                      float(spatial_scale), _p(out), _p(argmax), _s()), "roi_pool_fwd")
+    return out
+
+
+def roi_pool_bwd_gather(gout, argmax, n_images, h, w, rois, out, pooled_size=14, bin_step=1, spatial_scale=1.0 / 16, rois_per_image=0,
+                        image_offset=0, addend=None, addend_images=0, mask_ref=None, roi_count=None):
+    """deterministic gather-form RoIPool backward from the forward's `argmax`; `out` [n_images,h,w,C] (fp32 or gout.dtype) is fully
+    overwritten with cast((sum_of_roi_contributions [+ addend]) [* (mask_ref > 0)])."""
+    r, out_size, c = gout.shape[0], gout.shape[1], gout.shape[3]
+    assert argmax is not None and argmax.shape == gout.shape and argmax.dtype == torch.int32 and argmax.is_contiguous() and gout.is_contiguous()
+    assert out.shape == (n_images, h, w, c) and out.is_contiguous()
+    nb = lib().unit_roi_pool_bwd_gather_workspace_bytes(r)
+    ws = workspace(nb, gout.device, slot=1)
+    nb_alg = (gout.numel() * gout.element_size() + argmax.numel() * 4
+              + out.numel() * out.element_size() * (1 + (addend is not None) + (mask_ref is not None)))
+    with _timed("roi_pool_bwd_gather", 0.0, nb_alg,
+                nb_alg + (pooled_size * pooled_size - out_size * out_size) * r * c * (gout.element_size() + 4)):
+        check(lib().unit_roi_pool_bwd_gather(_p(gout), _p(argmax), dt(gout.dtype), n_images, h, w, c, _p(rois), _p(roi_count), r,
+                                             rois_per_image, image_offset, pooled_size, out_size, bin_step, float(spatial_scale),
+                                             _p(addend), addend_images, _p(mask_ref), _p(out), dt(out.dtype), _p(ws), ws.numel(), _s()),
+              "roi_pool_bwd_gather")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ losses
 BOX_LOSS_TYPES = {"smooth_l1": 0, "giou": 1}          # include/unit_hip.h: UNIT_BOXLOSS_SMOOTH_L1 / UNIT_BOXLOSS_GIOU
 
