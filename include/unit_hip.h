@@ -409,9 +409,20 @@ int unit_box_reg_loss(const float* bbox, int ld, int col0, int K, const int* lab
 int unit_box_reg_loss_ex(const float* bbox, int ld, int col0, int K, const int* labels, const float* rois5, const float* gt_boxes,
                          const float* weights4, int R, float gscale, float* loss, void* dy, int dy_dtype, int ldd, int dcol0,
                          unsigned long long* acc, int loss_type, float beta, void* stream);
+/* WSDDN / MIL (weak_detector_fast_rcnn.py:202-214, 257-260), one workgroup per image, images in fixed slots of S rows (valid[row] >= 0):
+ * xr_out [B*S][K] = softmax(cls / cls_temp, classes) * softmax(det / det_temp, the image's live rows), zero rows for empty slots;
+ * *loss = mil_multiplier * mean_{image, class} BCE(clamp(sum_r x_r, 1e-6, 1 - 1e-6), multihot); dy (may be NULL) gets gscale * d loss / d streams
+ * in columns [dyc0, +K) and [dyd0, +K), zero rows for empty slots, zero through a clamped class. K <= 96 (UNIT_ERR_ARG above).
+ * Order of the sums: within an image the wave partials are combined in wave order, so xr_out and dy are bit-reproducible. *loss is zeroed and
+ * then added to by one float atomic per image: its bits are reproducible for B <= 2 only (a + b = b + a); from three images on the arrival
+ * order of the workgroups decides the last bit. */
 int unit_wsddn_mil(const float* streams, int ld, int ccol0, int dcol0, int K, const int* valid, int S, int B,
                    const unsigned char* multihot, float cls_temp, float det_temp, float mil_multiplier, float gscale, float* loss,
                    float* xr_out, void* dy, int dy_dtype, int ldd, int dyc0, int dyd0, void* stream);
+/* OICR pseudo-label targets (weak_detector_fast_rcnn.py:353-408), one workgroup per image, one thread per slot: S <= 1024 and K <= 95
+ * (UNIT_ERR_ARG otherwise, nothing launched). The bound on K is one below unit_wsddn_mil's 96: K = 96 runs through MIL and is refused
+ * here, so a 96-class weak head cannot get its targets -- kept as it is and pinned by tests/test_weak_loss_ops_gpu.py::test_argument_checks.
+ * Ties go to the lowest index: the row of a class's largest probability (across waves too), the pseudo-GT of a row's largest IoU. */
 int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
                       const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, void* stream);
 /* unit_oicr_targets plus the box of the pseudo-GT that each row's Matcher picked -- the `gt_boxes` field of the proposals that
