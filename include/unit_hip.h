@@ -556,6 +556,35 @@ int unit_detection_offset_gather(const float* cand_boxes, const int* cand_class,
 int unit_detection_finalize(const float* cand_boxes, const float* cand_scores, const int* cand_class, const int* cand_roi, const int* order,
                             const int* keep, const int* keep_count, int B, int cap, int topk, float* out_boxes, float* out_scores,
                             int* out_class, int* out_roi, int* out_count, void* stream);
+/* class-segmented form of the NMS stage (between the score sort and unit_detection_finalize), for candidate lists beyond unit_nms's 65 536:
+ * after the batched_nms shift class * (cand_max[b] + 1) boxes of different classes never overlap, and a class holds at most one candidate per
+ * RoI, so the one all-pairs problem over `cap` candidates is K independent problems of at most Rcap boxes each.
+ *   unit_detection_class_segments  regroups each image's score-sorted candidates (`order` of the stable sort, the first cand_count[b]) by
+ *       class: a stable counting sort on the class id, so inside a class the candidates stay in descending-score order with ties in (RoI, class)
+ *       order. Segment s = b * K + class holds seg_count[s] <= Rseg slots: seg_boxes [B*K][Rseg][4] the boxes with the shift added (the float
+ *       operations of unit_detection_offset_gather, so every same-class IoU is the same float computation), seg_scores [B*K][Rseg], seg_pos
+ *       [B*K][Rseg] the slot's position in the image's global score order (ascending inside a segment). Slots behind seg_count[s] are not
+ *       written: unit_nms reads none of them. Rseg >= the largest class population; Rcap always suffices. Workspace:
+ *       unit_detection_segments_workspace_bytes(B, cap, K).
+ *   unit_nms  then runs on the B * K segments as images of capacity Rseg with max_keep = topk (workspace unit_nms_workspace_bytes(B * K,
+ *       Rseg)). That cut is exact: the global result is the first topk of the union of the per-class survivors in score order, a class
+ *       contributes at most topk entries to it, and they are its first ones -- greedy NMS never looks ahead, so stopping a class after topk
+ *       kept boxes changes nothing in front of the cut.
+ *   unit_detection_merge_keep  merges the K keep lists of an image (seg_keep [B*K][topk] in-segment indices as unit_nms wrote them,
+ *       seg_keep_count [B*K]) by global position: keep [B][topk] = the first topk of their union, ascending in position (descending score,
+ *       stable ties) as indices into the global sorted order, -1 behind keep_count[b] -- the form unit_detection_finalize consumes. keep_pos
+ *       int [B*K][topk] is scratch.
+ *   unit_detection_max_candidates  the largest `cap` of this form, the smallest of the limits that remain: DET_MAX_RCAP = 262 144 RoIs (x up to
+ *       96 classes) in unit_detection_candidates, 2^20 keys in the sorter, int positions with 4 coordinates each (2^31 / 4) -> 1 048 576.
+ *       Per class Rseg <= unit_nms_max_candidates() holds on top of it; unit_detection_segments_check applies every bound without a launch. */
+int unit_detection_max_candidates(void);
+int unit_detection_segments_check(int B, int cap, int K, int Rseg);
+size_t unit_detection_segments_workspace_bytes(int B, int cap, int K);
+int unit_detection_class_segments(const float* cand_boxes, const float* cand_scores, const int* cand_class, const int* order,
+                                  const int* cand_count, const float* cand_max, int B, int cap, int K, int Rseg, float* seg_boxes,
+                                  float* seg_scores, int* seg_count, int* seg_pos, void* workspace, size_t workspace_bytes, void* stream);
+int unit_detection_merge_keep(const int* seg_keep, const int* seg_keep_count, const int* seg_pos, int B, int K, int Rseg, int cap, int topk,
+                              int* keep_pos, int* keep, int* keep_count, void* stream);
 int unit_detector_postprocess(float* boxes, const int* count, int B, int topk, const float* scale_xy_dev, const float* out_hw_dev,
                               unsigned char* nonempty, void* stream);
 /* output assembly without stock operators (the reference: boolean-mask indexing per image and field, detectron2 detector_postprocess via

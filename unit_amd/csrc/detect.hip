@@ -601,6 +601,171 @@ extern "C" int unit_detection_finalize(const float* cand_boxes, const float* can
   return UNIT_OK;
 }
 
+// ---- class-segmented NMS stage: the K independent per-class problems instead of one all-pairs problem over the shifted list ----------
+// Boxes of different classes never overlap after the batched_nms shift and a class holds at most one candidate per RoI, so the score-sorted
+// list is regrouped by class (a stable counting sort on the class id, chip-wide: 256 sorted positions per workgroup), unit_nms runs on the
+// B * K segments of capacity Rseg, and the K keep lists of an image are merged back by global position.
+//  (1) det_seg_hist_kernel: class histogram of every 256-position tile -> hist [B][nblk][K]
+//  (2) det_seg_scan_kernel: per (image, class) the exclusive prefix over the tiles (in place) and the segment counts
+//  (3) det_seg_scatter_kernel: slot = tile base + the number of earlier positions of the tile with the same class (stable), writes the
+//      shifted box, the score and the global position
+#define DET_SEG_TILE 256
+#define DET_SORT_MAX_KEYS (1 << 20)          // unit_sort_desc_stable refuses more keys (1024 * SORT_THREADS, sort_nms.hip)
+extern "C" int unit_nms_max_candidates(void);          // sort_nms.hip: the capacity of one unit_nms problem, here of one class
+
+__device__ __forceinline__ int det_seg_class(const int* __restrict__ cclass, const int* __restrict__ order, int b, int i, int n, int cap, int K,
+                                             int* src_out) {
+  if (i >= n) return -1;
+  int src = order[(size_t)b * cap + i];
+  if ((unsigned)src >= (unsigned)cap) return -1;
+  int c = cclass[(size_t)b * cap + src];
+  *src_out = src;
+  return (unsigned)c < (unsigned)K ? c : -1;
+}
+
+__global__ void __launch_bounds__(DET_SEG_TILE) det_seg_hist_kernel(const int* __restrict__ cclass, const int* __restrict__ order,
+                                                                    const int* __restrict__ ccount, int cap, int K, int nblk,
+                                                                    int* __restrict__ hist) {
+  __shared__ int h[DET_MAXC];
+  int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+  if (tid < K) h[tid] = 0;
+  __syncthreads();
+  int n = min(ccount[b], cap), src;
+  int c = det_seg_class(cclass, order, b, blk * DET_SEG_TILE + tid, n, cap, K, &src);
+  if (c >= 0) atomicAdd(&h[c], 1);
+  __syncthreads();
+  if (tid < K) hist[((size_t)b * nblk + blk) * K + tid] = h[tid];
+}
+
+__global__ void __launch_bounds__(128) det_seg_scan_kernel(int* __restrict__ hist, int K, int nblk, int Rseg, int* __restrict__ seg_count) {
+  int b = blockIdx.x, k = threadIdx.x;
+  if (k >= K) return;
+  int* hb = hist + (size_t)b * nblk * K + k;
+  int run = 0;
+#pragma unroll 8
+  for (int blk = 0; blk < nblk; ++blk) { int t = hb[(size_t)blk * K]; hb[(size_t)blk * K] = run; run += t; }
+  seg_count[b * K + k] = min(run, Rseg);
+}
+
+__global__ void __launch_bounds__(DET_SEG_TILE) det_seg_scatter_kernel(const float* __restrict__ cboxes, const float* __restrict__ cscores,
+                                                                       const int* __restrict__ cclass, const int* __restrict__ order,
+                                                                       const int* __restrict__ ccount, const float* __restrict__ cmax, int cap,
+                                                                       int K, int nblk, int Rseg, const int* __restrict__ hist,
+                                                                       float* __restrict__ seg_boxes, float* __restrict__ seg_scores,
+                                                                       int* __restrict__ seg_pos) {
+  __shared__ int cls[DET_SEG_TILE];
+  int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
+  int n = min(ccount[b], cap), src = 0;
+  int i = blk * DET_SEG_TILE + tid;
+  int c = det_seg_class(cclass, order, b, i, n, cap, K, &src);
+  cls[tid] = c;
+  __syncthreads();
+  if (c < 0) return;
+  int rank = 0;
+  for (int j = 0; j < tid; ++j) rank += cls[j] == c ? 1 : 0;
+  int slot = hist[((size_t)b * nblk + blk) * K + c] + rank;
+  if (slot >= Rseg) return;          // (a class with more than Rseg candidates: more than one per RoI, not produced by unit_detection_candidates)
+  f32x4 v = *reinterpret_cast<const f32x4*>(cboxes + ((size_t)b * cap + src) * 4);
+  float off = (float)c * (cmax[b] + 1.0f);          // det_offset_gather_kernel's shift, the same float operations
+  v[0] += off; v[1] += off; v[2] += off; v[3] += off;
+  size_t o = ((size_t)b * K + c) * Rseg + slot;
+  *reinterpret_cast<f32x4*>(seg_boxes + 4 * o) = v;
+  seg_scores[o] = cscores[(size_t)b * cap + src];
+  seg_pos[o] = i;
+}
+
+extern "C" int unit_detection_max_candidates(void) {
+  long lim = (long)DET_MAX_RCAP * DET_MAXC;          // the candidate kernel: DET_MAX_RCAP RoIs of at most DET_MAXC classes
+  if (lim > DET_SORT_MAX_KEYS) lim = DET_SORT_MAX_KEYS;          // the sorter
+  if (lim > 0x7fffffffL / 4) lim = 0x7fffffffL / 4;          // int positions, 4 coordinates per candidate (the per-image offsets are size_t)
+  return (int)lim;
+}
+// every bound of the segmented form, without a launch (ops.detections asks before it starts the chain)
+extern "C" int unit_detection_segments_check(int B, int cap, int K, int Rseg) {
+  UNIT_CHECK_ARG(B >= 0 && K >= 1 && K <= DET_MAXC, "detection_class_segments: 1 to 96 classes");
+  UNIT_CHECK_ARG(cap >= 1 && cap <= unit_detection_max_candidates(), "detection_class_segments: more than 1048576 candidates per image");
+  UNIT_CHECK_ARG(Rseg >= 1 && Rseg <= cap, "detection_class_segments: the segment capacity must lie in 1 .. cap");
+  UNIT_CHECK_ARG(Rseg <= unit_nms_max_candidates(), "detection_class_segments: more than 65536 candidates per class (unit_nms)");
+  UNIT_CHECK_ARG((long)B * K <= 65535, "detection_class_segments: more than 65535 (image, class) segments");
+  return UNIT_OK;
+}
+extern "C" size_t unit_detection_segments_workspace_bytes(int B, int cap, int K) {
+  return (size_t)B * cdiv(cap > 0 ? cap : 1, DET_SEG_TILE) * K * sizeof(int);
+}
+extern "C" int unit_detection_class_segments(const float* cand_boxes, const float* cand_scores, const int* cand_class, const int* order,
+                                             const int* cand_count, const float* cand_max, int B, int cap, int K, int Rseg, float* seg_boxes,
+                                             float* seg_scores, int* seg_count, int* seg_pos, void* workspace, size_t workspace_bytes,
+                                             void* stream) {
+  int rc = unit_detection_segments_check(B, cap, K, Rseg);
+  if (rc != UNIT_OK) return rc;
+  if (workspace_bytes < unit_detection_segments_workspace_bytes(B, cap, K)) { unit_set_error("detection_class_segments: workspace too small"); return UNIT_ERR_WORKSPACE; }
+  if (B == 0) return UNIT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  int nblk = cdiv(cap, DET_SEG_TILE);
+  int* hist = (int*)workspace;
+  det_seg_hist_kernel<<<dim3(nblk, B), DET_SEG_TILE, 0, st>>>(cand_class, order, cand_count, cap, K, nblk, hist);
+  UNIT_LAUNCH_CHECK();
+  det_seg_scan_kernel<<<B, 128, 0, st>>>(hist, K, nblk, Rseg, seg_count);
+  UNIT_LAUNCH_CHECK();
+  det_seg_scatter_kernel<<<dim3(nblk, B), DET_SEG_TILE, 0, st>>>(cand_boxes, cand_scores, cand_class, order, cand_count, cand_max, cap, K, nblk,
+                                                                Rseg, hist, seg_boxes, seg_scores, seg_pos);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
+// merge of the K per-class keep lists of an image (each ascending in global position) into the first topk of their union, ascending: an
+// element's output rank is the number of kept positions below it over all K lists (positions are unique), found by binary search -- no LDS,
+// no atomics. det_keep_pos_kernel first turns the in-segment keep indices into global positions (INT_MAX behind a list's count).
+__global__ void __launch_bounds__(256) det_keep_pos_kernel(const int* __restrict__ seg_keep, const int* __restrict__ seg_keep_count,
+                                                           const int* __restrict__ seg_pos, int K, int Rseg, int topk, int* __restrict__ keep_pos,
+                                                           int* __restrict__ keep_count) {
+  int b = blockIdx.z, k = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+  size_t s = (size_t)b * K + k;
+  if (j < topk) {
+    int idx = j < min(seg_keep_count[s], topk) ? seg_keep[s * topk + j] : -1;
+    keep_pos[s * topk + j] = (unsigned)idx < (unsigned)Rseg ? seg_pos[s * Rseg + idx] : 0x7fffffff;
+  }
+  if (k == 0 && j == 0) {
+    long total = 0;
+    for (int q = 0; q < K; ++q) total += min(seg_keep_count[(size_t)b * K + q], topk);
+    keep_count[b] = (int)(total < topk ? total : topk);
+  }
+}
+
+__global__ void __launch_bounds__(256) det_merge_keep_kernel(const int* __restrict__ keep_pos, const int* __restrict__ keep_count, int K, int topk,
+                                                             int cap, int* __restrict__ keep) {
+  int b = blockIdx.z, k = blockIdx.y, j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= topk) return;
+  if (k == 0 && j >= keep_count[b]) keep[(size_t)b * topk + j] = -1;          // the tail behind the kept prefix
+  const int* kp = keep_pos + (size_t)b * K * topk;
+  int p = kp[(size_t)k * topk + j];
+  if ((unsigned)p >= (unsigned)cap) return;          // behind this list's count
+  int rank = j;                                      // its own list
+  for (int q = 0; q < K && rank < topk; ++q) {
+    if (q == k) continue;
+    const int* lq = kp + (size_t)q * topk;
+    int lo = 0, hi = topk;                           // first entry >= p (INT_MAX pads the list)
+    while (lo < hi) { int mid = (lo + hi) >> 1; if (lq[mid] < p) lo = mid + 1; else hi = mid; }
+    rank += lo;
+  }
+  if (rank < topk) keep[(size_t)b * topk + rank] = p;
+}
+
+extern "C" int unit_detection_merge_keep(const int* seg_keep, const int* seg_keep_count, const int* seg_pos, int B, int K, int Rseg, int cap,
+                                         int topk, int* keep_pos, int* keep, int* keep_count, void* stream) {
+  UNIT_CHECK_ARG(B >= 0 && K >= 1 && K <= DET_MAXC, "detection_merge_keep: 1 to 96 classes");
+  UNIT_CHECK_ARG(topk >= 1 && Rseg >= 1 && cap >= Rseg, "detection_merge_keep: topk and the segment capacity must be positive, cap >= Rseg");
+  UNIT_CHECK_ARG(B <= 65535, "detection_merge_keep: more than 65535 images");
+  if (B == 0) return UNIT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  dim3 grid(cdiv(topk, 256), K, B);
+  det_keep_pos_kernel<<<grid, 256, 0, st>>>(seg_keep, seg_keep_count, seg_pos, K, Rseg, topk, keep_pos, keep_count);
+  UNIT_LAUNCH_CHECK();
+  det_merge_keep_kernel<<<grid, 256, 0, st>>>(keep_pos, keep_count, K, topk, cap, keep);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
 // detector_postprocess (rcnn.py:411-429 -> detectron2): scale to the output resolution, clip, flag non-empty
 __global__ void postprocess_kernel(float* __restrict__ boxes, const int* __restrict__ count, int topk, const float* __restrict__ scale_xy,
                                    const float* __restrict__ out_hw, unsigned char* __restrict__ nonempty) {

@@ -119,14 +119,14 @@ def roi_heads_predict(rh, feat, props, pcount):
     return scores, bbox, sims
 
 
-def roi_heads_detect(rh, feat, probs, bbox, props, pcount, hw, sims, with_mask=True, want_similarity=False, cand_cap=None):
+def roi_heads_detect(rh, feat, probs, bbox, props, pcount, hw, sims, with_mask=True, want_similarity=False, cand_cap=None, nms=None):
     """the "detect" half: `inference` (fast_rcnn.py:455-468, fast_rcnn_inference) on class probabilities [N*Rcap, K+1] and deltas [N*Rcap, 4K]
-    -> forward_with_given_boxes (mask, roi_heads.py:776-781). Outputs as roi_heads_inference."""
+    -> forward_with_given_boxes (mask, roi_heads.py:776-781). Outputs as roi_heads_inference. cand_cap / nms: as ops.detections."""
     bp = rh.box_predictor
     n = props.shape[0]
     rcap = props.shape[1]
     boxes, sc, cls, roi, cnt = ops.detections(probs, bbox, props, pcount, hw, bp.bbox_reg_weights, bp.test_score_thresh,
-                                              bp.test_nms_thresh, bp.test_topk_per_image, cand_cap=cand_cap)
+                                              bp.test_nms_thresh, bp.test_topk_per_image, cand_cap=cand_cap, nms=nms)
     # a16 eval: forward_with_given_boxes (roi_heads.py:776-781) -> mask head on the detected boxes (before postprocess)
     mask_probs = None
     mh = getattr(rh, "mask_head", None)
@@ -277,21 +277,29 @@ def tta_predict(model, x, twin_batch=True, want_views=False):
     return out + (views, plan) if want_views else out
 
 
-def inference_tta(model, batched_inputs, do_postprocess=True, detected_instances=None, twin_batch=True):
+def tta_candidate_limit(num_classes):
+    """the candidates a TTA call may have per image: the class-segmented NMS stage's ceiling (ops.max_segmented_candidates(), the sorter's), and
+    no class above what one unit_nms problem takes (every proposal is a candidate of every class)"""
+    return min(ops.max_segmented_candidates(), ops.max_detection_candidates() * num_classes)
+
+
+def inference_tta(model, batched_inputs, do_postprocess=True, detected_instances=None, twin_batch=True, nms=None):
     """meta_arch/rcnn.py:495-527: per input, every view through backbone and ROI heads up to the predictor's [scores, deltas]; the class
     probabilities summed (not renormalised: scores up to n_views), the deltas averaged (the flipped views' dx as they are, :524), decoded once
     against the ORIGINAL proposals and their image_size, then fast_rcnn_inference and _postprocess. The branch never reaches
     forward_with_given_boxes, and on the mask ROI heads the reference does not get that far (TTA_MASK_HEADS). More than one input: the per-image procedure in a loop (the reference
-    asserts len == 1, :494)."""
+    asserts len == 1, :494). nms: the form of the NMS stage (ops.detections); by default the full form up to 65 536 candidates and the
+    class-segmented one above."""
     rh = model.roi_heads
     k = rh.num_classes
-    tta_check(model.cfg.TEST.AUG, batched_inputs, k, detected_instances, mask_on=getattr(rh, "mask_head", None) is not None)
+    tta_check(model.cfg.TEST.AUG, batched_inputs, k, detected_instances, candidate_limit=tta_candidate_limit(k),
+              mask_on=getattr(rh, "mask_head", None) is not None)
     results = []
     for x in batched_inputs:
         probs_sum, delta_mean, props, count, image_size = tta_predict(model, x, twin_batch)
         hw = model._sizes_on_device([image_size])
         boxes, sc, cls, roi, cnt, _ = roi_heads_detect(rh, None, probs_sum, delta_mean, props, count, hw, None, with_mask=False,
-                                                       cand_cap=props.shape[1] * k)
+                                                       cand_cap=props.shape[1] * k, nms=nms)
         # _postprocess (:539-540) is handed the LAST view's image sizes, read only where an input carries no "height" / "width"
         out_hw = None
         if do_postprocess:

@@ -1694,23 +1694,23 @@ def tta_accumulate(scores, deltas, k, r, v, n, probs_sum, delta_sum, delta_mean,
 
 
 def max_detection_candidates():
-    """the largest cand_cap `detections` takes: unit_nms's limit (the candidate kernel takes any cap, the sorter 2^20 keys)"""
+    """the largest cand_cap the full form of `detections` takes: unit_nms's limit (the candidate kernel takes any cap, the sorter 2^20 keys)"""
     return int(lib().unit_nms_max_candidates())
 
 
-def detections(probs, deltas, props, pcount, image_hw, weights, score_thresh, nms_thresh, topk, cand_cap=None):
-    """fast_rcnn_inference for B images: probs [B*Rcap, K+1], deltas [B*Rcap, 4K], props [B,Rcap,4], pcount [B] (device)
-    -> (boxes [B,topk,4], scores [B,topk], classes [B,topk], roi_idx [B,topk], count [B]); rows past count[b] hold 0 / 0 / -1 / -1.
-    Non-finite predictions: a RoI is dropped WHOLE when any of its K decoded boxes (before clipping; a NaN dw / dh is not clamped away)
-    or any of its K+1 scores, background included, is non-finite -- detectron2's row filter in fast_rcnn_inference_single_image.
-    roi_idx counts the image's ORIGINAL proposal rows (gather_rows on similarity['seg'] needs those); the reference reports indices into
-    its filtered rows, which differ once a row was dropped.
-    Ties in score keep (RoI, class) order (stable sort). More than `cand_cap` candidates above the threshold (default min(Rcap * K,
-    65536)): the first cand_cap in (RoI, class) order go on to the sort and NMS, the rest are cut silently, whatever their scores."""
+def max_segmented_candidates():
+    """the largest cand_cap the class-segmented form of `detections` takes (unit_detection_max_candidates: the sorter's 2^20 keys); on top of
+    it a class holds at most max_detection_candidates() candidates, that is Rcap <= 65536"""
+    return int(lib().unit_detection_max_candidates())
+
+
+def detection_candidates(probs, deltas, props, pcount, image_hw, weights, score_thresh, cap):
+    """the first stages of `detections`: unit_detection_candidates and the stable score sort -> (boxes [B,cap,4] clipped, scores [B,cap],
+    classes int32 [B,cap], RoI rows int32 [B,cap] in (RoI, class) order, count int32 [B], max coordinate fp32 [B], order int32 [B,cap]: the
+    candidate at each position of the descending score order, defined up to count[b])"""
     b, rcap = props.shape[0], props.shape[1]
     k = deltas.shape[1] // 4
     dev = probs.device
-    cap = cand_cap or min(rcap * k, 65536)
     cb = torch.empty((b, cap, 4), dtype=torch.float32, device=dev)
     cs = zeros((b, cap), torch.float32, dev)
     cc = torch.empty((b, cap), dtype=torch.int32, device=dev)
@@ -1724,9 +1724,89 @@ def detections(probs, deltas, props, pcount, image_hw, weights, score_thresh, nm
     # stable descending sort of the candidate scores (unused tail slots hold 0 <= thresh and sort behind every candidate)
     # (chip-wide select + rank sort over the valid candidates only: every valid score is > score_thresh >= 0 = the fill value)
     _, order = sort_desc(cs, b, cap, topk=cap, min_exclusive=0.0 if score_thresh >= 0 else None)
-    ob = torch.empty((b, cap, 4), dtype=torch.float32, device=dev)
-    check(lib().unit_detection_offset_gather(_p(cb), _p(cc), _p(order), _p(cnt), _p(cmax), b, cap, _p(ob), _s()), "detection_offset_gather")
-    keep, kc, _, _ = nms(ob, cs, cnt, nms_thresh, topk)
+    return cb, cs, cc, cr, cnt, cmax, order
+
+
+def detection_class_segments(cb, cs, cc, order, cnt, cmax, k, rseg):
+    """the score-sorted candidates regrouped by class (unit_detection_class_segments) -> (seg_boxes [B*K,Rseg,4] shifted, seg_scores [B*K,Rseg],
+    seg_count int32 [B*K], seg_pos int32 [B*K,Rseg]: the slot's position in its image's score order); slots behind seg_count are unwritten"""
+    b, cap = cs.shape
+    dev = cs.device
+    sb = torch.empty((b * k, rseg, 4), dtype=torch.float32, device=dev)
+    ss = torch.empty((b * k, rseg), dtype=torch.float32, device=dev)
+    sp = torch.empty((b * k, rseg), dtype=torch.int32, device=dev)
+    sn = torch.empty((b * k,), dtype=torch.int32, device=dev)
+    nb = lib().unit_detection_segments_workspace_bytes(b, cap, k)
+    ws = workspace(nb, dev)
+    check(lib().unit_detection_class_segments(_p(cb), _p(cs), _p(cc), _p(order), _p(cnt), _p(cmax), b, cap, k, rseg, _p(sb), _p(ss), _p(sn),
+                                              _p(sp), _p(ws), ws.numel(), _s()), "detection_class_segments")
+    return sb, ss, sn, sp
+
+
+def detection_merge_keep(seg_keep, seg_kc, seg_pos, b, k, cap):
+    """the K per-class keep lists of every image merged by global position (unit_detection_merge_keep) -> (keep [B,topk] indices into the
+    global score order, -1 behind the kept prefix; keep_count int32 [B])"""
+    topk, rseg = seg_keep.shape[1], seg_pos.shape[1]
+    dev = seg_keep.device
+    kpos = torch.empty((b * k, topk), dtype=torch.int32, device=dev)
+    keep = torch.empty((b, topk), dtype=torch.int32, device=dev)
+    kc = torch.empty((b,), dtype=torch.int32, device=dev)
+    check(lib().unit_detection_merge_keep(_p(seg_keep), _p(seg_kc), _p(seg_pos), b, k, rseg, cap, topk, _p(kpos), _p(keep), _p(kc), _s()),
+          "detection_merge_keep")
+    return keep, kc
+
+
+def segmented_nms(cb, cs, cc, order, cnt, cmax, k, rseg, nms_thresh, topk, want_parts=False):
+    """the NMS stage of `detections` in its class-segmented form: class segments -> unit_nms on the B * K segments (max_keep = topk, exact: a
+    class cannot put more than topk boxes into the global top topk) -> merge. -> (keep [B,topk], keep_count [B]) as `nms` returns them.
+    want_parts: additionally (seg_count, seg_pos, seg_keep, seg_keep_count), for the tests"""
+    b, cap = cs.shape
+    dev = cs.device
+    sb, ss, sn, sp = detection_class_segments(cb, cs, cc, order, cnt, cmax, k, rseg)
+    skeep = torch.empty((b * k, topk), dtype=torch.int32, device=dev)          # unit_nms writes the tails (-1) itself
+    skc = torch.empty((b * k,), dtype=torch.int32, device=dev)
+    nb = lib().unit_nms_workspace_bytes(b * k, rseg)
+    ws = workspace(nb, dev)
+    with _timed("nms_segmented", 0.0, b * cap * 20.0):
+        check(lib().unit_nms(_p(sb), _p(ss), _p(sn), b * k, rseg, float(nms_thresh), topk, _p(skeep), _p(skc), None, None, _p(ws), ws.numel(),
+                             _s()), "nms")
+    keep, kc = detection_merge_keep(skeep, skc, sp, b, k, cap)
+    return (keep, kc, (sn, sp, skeep, skc)) if want_parts else (keep, kc)
+
+
+_full_nms = nms          # (`detections` has a keyword of that name)
+
+
+def detections(probs, deltas, props, pcount, image_hw, weights, score_thresh, nms_thresh, topk, cand_cap=None, nms=None):
+    """fast_rcnn_inference for B images: probs [B*Rcap, K+1], deltas [B*Rcap, 4K], props [B,Rcap,4], pcount [B] (device)
+    -> (boxes [B,topk,4], scores [B,topk], classes [B,topk], roi_idx [B,topk], count [B]); rows past count[b] hold 0 / 0 / -1 / -1.
+    Non-finite predictions: a RoI is dropped WHOLE when any of its K decoded boxes (before clipping; a NaN dw / dh is not clamped away)
+    or any of its K+1 scores, background included, is non-finite -- detectron2's row filter in fast_rcnn_inference_single_image.
+    roi_idx counts the image's ORIGINAL proposal rows (gather_rows on similarity['seg'] needs those); the reference reports indices into
+    its filtered rows, which differ once a row was dropped.
+    Ties in score keep (RoI, class) order (stable sort). More than `cand_cap` candidates above the threshold (default min(Rcap * K,
+    65536)): the first cand_cap in (RoI, class) order go on to the sort and NMS, the rest are cut silently, whatever their scores.
+    nms: the form of the NMS stage. "full": one all-pairs problem over the class-shifted list (unit_nms; cand_cap <=
+    max_detection_candidates() = 65536, workspace quadratic in cand_cap). "segmented": one problem per (image, class) of at most Rcap boxes
+    and a merge by score order (cand_cap <= max_segmented_candidates(), Rcap <= 65536; refused before anything launches otherwise). Both give
+    the same result bit for bit. None: "full" where it fits, "segmented" above it -- a caller may pass a cand_cap up to Rcap * K beyond 65536."""
+    b, rcap = props.shape[0], props.shape[1]
+    k = deltas.shape[1] // 4
+    dev = probs.device
+    cap = cand_cap or min(rcap * k, 65536)
+    if nms not in (None, "full", "segmented"):
+        raise ValueError("detections: nms must be None, 'full' or 'segmented'")
+    segmented = nms == "segmented" or (nms is None and cap > max_detection_candidates())
+    rseg = max(min(rcap, cap), 1)          # a RoI contributes at most one candidate per class
+    if segmented:
+        check(lib().unit_detection_segments_check(b, cap, k, rseg), "detection_class_segments")
+    cb, cs, cc, cr, cnt, cmax, order = detection_candidates(probs, deltas, props, pcount, image_hw, weights, score_thresh, cap)
+    if segmented:
+        keep, kc = segmented_nms(cb, cs, cc, order, cnt, cmax, k, rseg, nms_thresh, topk)
+    else:
+        ob = torch.empty((b, cap, 4), dtype=torch.float32, device=dev)
+        check(lib().unit_detection_offset_gather(_p(cb), _p(cc), _p(order), _p(cnt), _p(cmax), b, cap, _p(ob), _s()), "detection_offset_gather")
+        keep, kc, _, _ = _full_nms(ob, cs, cnt, nms_thresh, topk)
     oboxes = torch.empty((b, topk, 4), dtype=torch.float32, device=dev)
     oscores = torch.empty((b, topk), dtype=torch.float32, device=dev)
     ocls = torch.empty((b, topk), dtype=torch.int32, device=dev)
