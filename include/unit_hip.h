@@ -433,6 +433,17 @@ int unit_oicr_targets(const float* src, int ld, int col0, int mode, int K, const
 int unit_oicr_targets_ex(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
                          const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, float* gt_boxes,
                          void* stream);
+/* The wide form of unit_oicr_targets_ex for MODEL.LOAD_PROPOSALS (every proposal of a weak image reaches the weak head): the same arguments
+ * and, row for row, the same results -- bit for bit those of unit_oicr_targets_ex wherever both run (S <= 1024) -- for
+ * 1 <= S <= unit_oicr_targets_max_rows() = 8192 rows per image and K <= 95 (UNIT_ERR_ARG otherwise, nothing launched, outputs untouched).
+ * One workgroup of 1024 threads per image; thread t owns rows t, t + 1024, ... (at most 8, their softmax statistics in registers). Ties go
+ * to the lowest row index whether the rival row belongs to the same thread, another thread or another wave. gt_boxes may be NULL. The
+ * narrow entries keep their S <= 1024 bound; the model takes this one only above it. */
+int unit_oicr_targets_wide(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S, int B,
+                           const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights, float* gt_boxes,
+                           void* stream);
+/* the largest S unit_oicr_targets_wide takes (8192: 1024 threads x 8 rows) */
+int unit_oicr_targets_max_rows(void);
 /* oicr_mean_scores (weak_detector_fast_rcnn.py:248): out[r, 0..K] = (sum_t softmax(logits[r, col0 + t*step : +K+1])) / n over the n
  * refinement streams, added in stream order, each softmax as unit_softmax_rows computes it; rows with valid[r] < 0 (valid may be NULL) are
  * written as zeros. The two targets kernels read the result in mode 0 (first K columns, ld = ldo). */

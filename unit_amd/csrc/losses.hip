@@ -934,6 +934,111 @@ extern "C" int unit_oicr_targets(const float* src, int ld, int col0, int mode, i
   return unit_oicr_targets_ex(src, ld, col0, mode, K, rois5, valid, S, B, multihot, fg_thresh, bg_thresh, labels, weights, nullptr, stream);
 }
 
+// The wide form (MODEL.LOAD_PROPOSALS: every proposal of a weak image, up to PRECOMPUTED_PROPOSAL_TOPK_TRAIN rows): the same workgroup per
+// image, 1024 threads, thread t owns rows t, t + 1024, ... -- at most OICR_WIDE_SLOTS of them, their softmax statistics and two 8-bit masks
+// (live, zeroed) in registers (every slot loop is unrolled: static indices, nothing in scratch). Per class a thread first takes the argmax
+// of its own rows in ascending slot (= ascending row) order with a strict >, then the wave and the workgroup combine (value, row) pairs
+// under the narrow kernel's rule, so the lowest row wins a tie wherever its rival sits. Everything per row is the narrow kernel's
+// expression, evaluated in its order.
+#define OICR_WIDE_THREADS 1024
+#define OICR_WIDE_SLOTS 8
+__global__ __launch_bounds__(OICR_WIDE_THREADS) void oicr_targets_wide_kernel(
+    const float* __restrict__ src, int ld, int col0, int mode, int K, const float* __restrict__ rois5, const int* __restrict__ valid, int S,
+    const unsigned char* __restrict__ multihot, float fg_thresh, float bg_thresh, int* __restrict__ labels, float* __restrict__ weights,
+    float* __restrict__ gt_boxes /* [B*S][4] or null */) {
+  __shared__ float s_val[16]; __shared__ int s_idx[16];
+  __shared__ f32x4 gbox[MIL_MAXK]; __shared__ float gscore[MIL_MAXK]; __shared__ int gcls[MIL_MAXK];
+  __shared__ int s_zero_row, s_ngt;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int ncol = mode == 0 ? K : K + 1;
+  const size_t base = (size_t)b * S;
+  unsigned havem = 0, zerom = 0;          // bit j: row tid + j * 1024 is live / was a class's winner
+  float mx[OICR_WIDE_SLOTS], se[OICR_WIDE_SLOTS];
+#pragma unroll
+  for (int j = 0; j < OICR_WIDE_SLOTS; ++j) {
+    const int r = tid + j * OICR_WIDE_THREADS;
+    mx[j] = 0.f; se[j] = 1.f;
+    if (r < S && valid[base + r] >= 0) {
+      havem |= 1u << j;
+      if (mode == 1) {
+        const float* xrow = src + (base + r) * ld + col0;
+        float m = -INFINITY;
+        for (int c = 0; c < ncol; ++c) m = fmaxf(m, xrow[c]);
+        float s = 0.f;
+        for (int c = 0; c < ncol; ++c) s += expf(xrow[c] - m);
+        mx[j] = m; se[j] = s;
+      }
+    }
+  }
+  if (tid == 0) s_ngt = 0;
+  __syncthreads();
+  for (int c = 0; c < K; ++c) {
+    if (!multihot[(size_t)b * K + c]) continue;     // wave-uniform (same for the whole block)
+    float v = -INFINITY; int idx = tid;
+#pragma unroll
+    for (int j = 0; j < OICR_WIDE_SLOTS; ++j) {
+      const int r = tid + j * OICR_WIDE_THREADS;
+      float cand = -INFINITY;
+      if (havem >> j & 1u) {
+        const float* xrow = src + (base + r) * ld + col0;
+        cand = (zerom >> j & 1u) ? 0.f : (mode == 0 ? xrow[c] : expf(xrow[c] - mx[j]) / se[j]);
+      }
+      if (j == 0 || cand > v) { v = cand; idx = r; }          // own rows in ascending order: the first of equals stays
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      float ov = __shfl_xor(v, o, 64); int oi = __shfl_xor(idx, o, 64);
+      if (ov > v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+    }
+    if ((tid & 63) == 0) { s_val[tid >> 6] = v; s_idx[tid >> 6] = idx; }
+    __syncthreads();
+    if (tid == 0) {
+      float bv = s_val[0]; int bi = s_idx[0];
+      for (int w = 1; w < OICR_WIDE_THREADS / 64; ++w)
+        if (s_val[w] > bv || (s_val[w] == bv && s_idx[w] < bi)) { bv = s_val[w]; bi = s_idx[w]; }
+      int g = s_ngt;
+      gscore[g] = bv; gcls[g] = c; s_zero_row = bi;
+      size_t rr = base + bi;
+      gbox[g] = f32x4{rois5[rr * 5 + 1], rois5[rr * 5 + 2], rois5[rr * 5 + 3], rois5[rr * 5 + 4]};
+      s_ngt = g + 1;
+    }
+    __syncthreads();
+    const int zr = s_zero_row;
+    if ((zr & (OICR_WIDE_THREADS - 1)) == tid) zerom |= 1u << (zr / OICR_WIDE_THREADS);          // cls_prob[max_index, :] = 0 (:364)
+    __syncthreads();
+  }
+  const int ng = s_ngt;
+#pragma unroll
+  for (int j = 0; j < OICR_WIDE_SLOTS; ++j) {
+    const int r = tid + j * OICR_WIDE_THREADS;
+    if (r >= S) continue;
+    const size_t row = base + r;
+    f32x4* gout = gt_boxes ? reinterpret_cast<f32x4*>(gt_boxes) + row : nullptr;
+    if (!(havem >> j & 1u)) { labels[row] = -1; weights[row] = 0.f; if (gout) *gout = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+    if (ng == 0) { labels[row] = K; weights[row] = 0.f; if (gout) *gout = f32x4{0.f, 0.f, 0.f, 0.f}; continue; }
+    f32x4 me = {rois5[row * 5 + 1], rois5[row * 5 + 2], rois5[row * 5 + 3], rois5[row * 5 + 4]};
+    float best = -1.f; int bi = 0;
+    for (int g = 0; g < ng; ++g) { float v = iou_box(gbox[g], me); if (v > best) { best = v; bi = g; } }
+    int lab = (best >= fg_thresh) ? gcls[bi] : K;
+    float w = gscore[bi];
+    if (best < bg_thresh) w = 0.f;
+    labels[row] = lab; weights[row] = w;
+    if (gout) *gout = gbox[bi];
+  }
+}
+extern "C" int unit_oicr_targets_max_rows(void) { return OICR_WIDE_THREADS * OICR_WIDE_SLOTS; }
+extern "C" int unit_oicr_targets_wide(const float* src, int ld, int col0, int mode, int K, const float* rois5, const int* valid, int S,
+                                      int B, const unsigned char* multihot, float fg_thresh, float bg_thresh, int* labels, float* weights,
+                                      float* gt_boxes, void* stream) {
+  UNIT_CHECK_ARG(K < MIL_MAXK && S >= 1 && S <= OICR_WIDE_THREADS * OICR_WIDE_SLOTS, "oicr_targets_wide: K >= 96 or S outside [1, 8192]");
+  UNIT_CHECK_ARG(((uintptr_t)gt_boxes & 15) == 0, "oicr_targets_wide: gt_boxes must be 16-byte aligned");
+  if (B == 0) return UNIT_OK;
+  oicr_targets_wide_kernel<<<B, OICR_WIDE_THREADS, 0, (hipStream_t)stream>>>(src, ld, col0, mode, K, rois5, valid, S, multihot, fg_thresh,
+                                                                             bg_thresh, labels, weights, gt_boxes);
+  UNIT_LAUNCH_CHECK();
+  return UNIT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // a12  regression branch: oicr_mean_scores  weak_detector_fast_rcnn.py:248
 //   out[r, 0..K] = (sum_t softmax(logits[r, col0 + t*step : +K+1])) / n, streams added in order (torch.mean over the stack); the per-row

@@ -134,13 +134,16 @@ class WeakDetectorOutputsBase(nn.Module):
         kernel instead of behind it. Every launch writes its own columns of dy / its own loss slot."""
         k = self.num_classes
         dy = ops.zeros((lin.shape[0], self.group.kp), grad_dtype, lin.device)
+        # more than 1024 rows per image (MODEL.LOAD_PROPOSALS): the targets kernel's wide form; at or below, the launch it always was
+        wide = dict(wide=True) if rois_per_image > 1024 else {}
 
         def oicr(it, xr):
             if it == 0:
-                lab, wts = ops.oicr_targets(xr, 0, 0, k, rois5, valid, rois_per_image, n_images, multihot, self.fg_threshold, self.bg_threshold)
+                lab, wts = ops.oicr_targets(xr, 0, 0, k, rois5, valid, rois_per_image, n_images, multihot, self.fg_threshold, self.bg_threshold,
+                                            **wide)
             else:
                 lab, wts = ops.oicr_targets(lin, self.col_oicr[it - 1], 1, k, rois5, valid, rois_per_image, n_images, multihot,
-                                            self.fg_threshold, self.bg_threshold)
+                                            self.fg_threshold, self.bg_threshold, **wide)
             ops.softmax_ce(lin, self.col_oicr[it], k + 1, lab, weights=wts, dy=dy, dcol0=self.col_oicr[it], loss_out=loss_out[1 + it:2 + it])
 
         def regression():
@@ -154,7 +157,7 @@ class WeakDetectorOutputsBase(nn.Module):
                 lab, wts, gtb = t["labels"][0], t["cls_weights"][0], t["gt_boxes"][0]
             else:
                 lab, wts, gtb = ops.oicr_targets(mean, 0, 0, k, rois5, valid, rois_per_image, n_images, multihot, self.fg_threshold,
-                                                 self.bg_threshold, want_boxes=True)
+                                                 self.bg_threshold, want_boxes=True, **wide)
             ops.softmax_ce(lin, self.col_reg_cls, k + 1, lab, weights=wts, dy=dy, dcol0=self.col_reg_cls, loss_out=reg_loss_out[0:1])
             ops.box_reg_loss(lin, self.col_reg_bbox, k, lab, rois5, gtb, self.bbox_reg_weights, dy=dy, dcol0=self.col_reg_bbox,
                              loss_out=reg_loss_out[1:2], loss_type=self.box_reg_loss_type, beta=self.smooth_l1_beta)

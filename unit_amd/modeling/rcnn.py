@@ -500,7 +500,8 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         # a7 RoI sampling (supervised) + first-512 weak proposals ; a8 RoIAlign on all RoIs at once
         s = rh.batch_size_per_image
         c.roi_cls, c.roi_gt = None, None
-        rs, rw = n_sup * s, n_weak * (s // rh.weak_divisor)
+        c.sw = sw = rh.weak_rows_per_image(props)          # (MODEL.LOAD_PROPOSALS: every proposal slot of a weak image)
+        rs, rw = n_sup * s, n_weak * sw
         c.rois = torch.empty((rs + rw, 5), dtype=torch.float32, device=self.device)          # supervised RoIs, then weak: both samplers write their rows
         if n_sup > 0:
             _, c.roi_cls, c.roi_gt, c.roi_counts = rh.label_and_sample_proposals(props[:n_sup], pcount[:n_sup], batch.gt_boxes,
@@ -670,7 +671,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         if rw > 0:
             # REGRESSION_BRANCH: the weak head's two further losses take the slots behind LOSS_NAMES (self.loss_names)
             reg_kw = dict(reg_loss_out=c.losses[len(LOSS_NAMES):]) if bp.weak_detector_head.regression_branch else {}
-            c.dy_weak = bp.weak_detector_head.fused_losses(lin_weak_w, c.rois[rs:], c.weak_valid, s // rh.weak_divisor, n_weak,
+            c.dy_weak = bp.weak_detector_head.fused_losses(lin_weak_w, c.rois[rs:], c.weak_valid, c.sw, n_weak,
                                                      batch.multihot, c.losses[2:6], dt,
                                                      side_stream=self._rpn_stream if self._streams_on() else None, **reg_kw)
         if sup_side is not None:
@@ -1029,7 +1030,7 @@ class WeaklySupervisedRCNNNoMeta(nn.Module):
         _, fh, fw, _ = c.feat.shape
         head, _ = rpn.rpn_head.fwd(feat, save=False)
         c.proposals = props, _, pcount = rpn.predict_proposals(head, rpn.anchor_generator.grid(fh, fw), self._sizes_on_device(sizes), True)
-        sw = rh.batch_size_per_image // rh.weak_divisor          # roi_heads.py:566-572: the first proposals of every image
+        sw = rh.weak_rows_per_image(props)          # roi_heads.py:566-572: the first proposals of every image (all of them: LOAD_PROPOSALS)
         c.rs, c.rw = 0, batch.n_weak * sw
         c.rois, c.weak_valid = rh.weak_rois(props, pcount, 0)
         pooled, c.pool_argmax = rh.pool_train(c.feat, c.rois)

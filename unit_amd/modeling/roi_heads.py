@@ -8,7 +8,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from ..structures import FAST_RCNN_REGISTRY, ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY, ShapeSpec
+from ..structures import FAST_RCNN_REGISTRY, PROPOSAL_GENERATOR_REGISTRY, ROI_BOX_HEAD_REGISTRY, ROI_HEADS_REGISTRY, ShapeSpec
 
 _FUSED = ("training runs inside WeaklySupervisedRCNNNoMeta's fused step (one explicit forward + backward plan over the HIP "
           "kernels, no autograd graph through the ROI heads): call the meta-architecture / engine.TrainerNoMeta.run_step")
@@ -48,6 +48,8 @@ class WSROIHeadNoMeta(nn.Module):
         self.iou_thresholds, self.iou_labels = list(rh.IOU_THRESHOLDS), list(rh.IOU_LABELS)
         self.proposal_append_gt = rh.PROPOSAL_APPEND_GT
         self.weak_divisor = rh.WEAK_CLASSIFIER_PROPOSAL_DIVISOR
+        # roi_heads.py:184, :566-572: with the switch on the weak images' proposals are not cut to their first S // divisor rows
+        self.load_proposals = bool(cfg.MODEL.LOAD_PROPOSALS)
         self.pooler_resolution = cfg.MODEL.ROI_BOX_HEAD.POOLER_RESOLUTION
         self.pooler_scale = 1.0 / 16
         self.sampling_ratio = cfg.MODEL.ROI_BOX_HEAD.POOLER_SAMPLING_RATIO
@@ -65,6 +67,10 @@ class WSROIHeadNoMeta(nn.Module):
         self.box_head = ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, pooled)
         self.weak_box_head = ROI_BOX_HEAD_REGISTRY.get(cfg.MODEL.ROI_BOX_HEAD.NAME)(cfg, pooled) if rh.MULTI_BOX_HEAD else None
         self.box_predictor = FAST_RCNN_REGISTRY.get(rh.FAST_RCNN.NAME)(cfg, self.box_head.output_shape)
+        if self.load_proposals and cfg.MODEL.PROPOSAL_GENERATOR.NAME in PROPOSAL_GENERATOR_REGISTRY:
+            # an RPN of this project hands every weak image POST_NMS_TOPK_TRAIN proposal slots: the row count is known here, so it is refused
+            # here; proposals that are handed in are counted when they arrive (weak_rows_per_image)
+            self.check_weak_rows(cfg.MODEL.RPN.POST_NMS_TOPK_TRAIN, "MODEL.RPN.POST_NMS_TOPK_TRAIN")
         self._base_classes = list(cfg.DATASETS.FEWSHOT.BASE_CLASSES_ID)
         self._novel_classes = list(cfg.DATASETS.FEWSHOT.NOVEL_CLASSES_ID)
         self.terms = {"cls": list(rh.FINETUNE_TERMS.CLASSIFIER), "bbox": list(rh.FINETUNE_TERMS.BBOX)}
@@ -123,9 +129,34 @@ class WSROIHeadNoMeta(nn.Module):
         self._last_sampling = (sidx, idx)        # mask head: gt_masks[matched_idx[sampled]] (select + crop_and_resize)
         return rois5, roi_cls, roi_gt, counts
 
-    # ---- roi_heads.py:566-572: the first 512//divisor RPN outputs of every weak image, no GT, no sampling
+    # ---- roi_heads.py:566-572: the first 512//divisor RPN outputs of every weak image, no GT, no sampling -- or, under MODEL.LOAD_PROPOSALS,
+    # every proposal of the image (the reference skips the cut): as many slots per image as the proposal tensor has
+    PCL_MAX_WEAK_ROWS = 2048          # unit_pcl_targets' ceiling (csrc/pcl.hip PT_SMAX: its tables live in LDS)
+
+    def check_weak_rows(self, rows, source="the proposals handed in"):
+        """UnsupportedConfig, before anything is launched, when MODEL.LOAD_PROPOSALS asks the weak detector for more rows per image than its
+        targets kernel takes: unit_oicr_targets_wide's ops.max_weak_rows() for TYPE "OICR", unit_pcl_targets' 2048 for TYPE "PCL" """
+        if rows <= 1024:          # (what both narrow targets kernels take)
+            return
+        wtype = self.box_predictor.weak_detector_head.weak_detector_type
+        limit = self.PCL_MAX_WEAK_ROWS if wtype == "PCL" else ops.max_weak_rows()
+        if rows > limit:
+            from .inference import UnsupportedConfig
+            raise UnsupportedConfig(f"MODEL.LOAD_PROPOSALS: True sends every proposal of a weak image to the weak detector: {rows} rows per image "
+                                    f"({source}), and WEAK_DETECTOR.TYPE {wtype!r} takes at most {limit}. Lower "
+                                    "MODEL.RPN.POST_NMS_TOPK_TRAIN / DATASETS.PRECOMPUTED_PROPOSAL_TOPK_TRAIN or switch MODEL.LOAD_PROPOSALS off")
+
+    def weak_rows_per_image(self, props):
+        """how many RoI slots a weak image gets: BATCH_SIZE_PER_IMAGE // WEAK_CLASSIFIER_PROPOSAL_DIVISOR, or with MODEL.LOAD_PROPOSALS the
+        row capacity of its proposal tensor `props` [N, P, 4] (slots past an image's own count are empty: valid = -1)"""
+        if not self.load_proposals:
+            return self.batch_size_per_image // self.weak_divisor
+        rows = int(props.shape[1])
+        self.check_weak_rows(rows)
+        return rows
+
     def weak_rois(self, props, pcount, batch_index_offset, rois_out=None):
-        return ops.first_k_rois(props, pcount, self.batch_size_per_image // self.weak_divisor, batch_index_offset, rois_out=rois_out)
+        return ops.first_k_rois(props, pcount, self.weak_rows_per_image(props), batch_index_offset, rois_out=rois_out)
 
     @property
     def max_pool(self):

@@ -196,7 +196,8 @@ class _HeadsFn(torch.autograd.Function):
         feat_w = ops.as_f32(_nhwc(fw, dtype)) if has_weak else None
         n_weak = feat_w.shape[0] if has_weak else 0
         s = rh.batch_size_per_image
-        sw = s // rh.weak_divisor
+        wprops, wcount = pack_proposal_instances(io["weak_proposals"], dev) if has_weak else (None, None)
+        sw = rh.weak_rows_per_image(wprops) if has_weak else s // rh.weak_divisor
         rs, rw = n_sup * s, n_weak * sw
         props, pcount = pack_proposal_instances(io["proposals"], dev)
         gt_boxes, gt_classes, gt_count = _pack_gt(io["targets"], dev)
@@ -212,7 +213,6 @@ class _HeadsFn(torch.autograd.Function):
         _, roi_cls, roi_gt, _ = rh.label_and_sample_proposals(props, pcount, gt_boxes, gt_classes, gt_count, perm, rois_out=rois[:rs])
         weak_valid = None
         if has_weak:
-            wprops, wcount = pack_proposal_instances(io["weak_proposals"], dev)
             _, weak_valid = rh.weak_rois(wprops, wcount, n_sup, rois_out=rois[rs:])
         osz = rh.pool_out[0]
         pooled = torch.empty((rs + rw, osz, osz, feat.shape[3]), dtype=feat.dtype, device=dev)
@@ -393,8 +393,8 @@ class _WeakHeadsFn(torch.autograd.Function):
         feat_w = ops.as_f32(_nhwc(fw, dtype))
         dev = feat_w.device
         n_weak = feat_w.shape[0]
-        sw = rh.batch_size_per_image // rh.weak_divisor
         wprops, wcount = pack_proposal_instances(io["weak_proposals"], dev)
+        sw = rh.weak_rows_per_image(wprops)
         rois, weak_valid = rh.weak_rois(wprops, wcount, 0)
         pooled, argmax = rh.pool_train(feat_w, rois)
         head = rh.weak_box_head if rh.weak_box_head is not None else rh.box_head

@@ -1488,14 +1488,26 @@ def wsddn_mil(streams, ccol0, dcol0, k, valid, s, b, multihot, cls_temp, det_tem
     return loss, xr
 
 
-def oicr_targets(src, col0, mode, k, rois5, valid, s, b, multihot, fg_thresh=0.5, bg_thresh=0.1, want_boxes=False):
+def max_weak_rows():
+    """the most rows per image `oicr_targets(..., wide=True)` takes (unit_oicr_targets_max_rows: 8192)"""
+    return int(lib().unit_oicr_targets_max_rows())
+
+
+def oicr_targets(src, col0, mode, k, rois5, valid, s, b, multihot, fg_thresh=0.5, bg_thresh=0.1, want_boxes=False, wide=False):
     """want_boxes (the regression branch): -> (labels, weights, gt_boxes [b * s, 4]), the box of the pseudo-GT each row was matched to
-    (unit_oicr_targets_ex); the plain form keeps its own export, so a model without the branch launches what it always did"""
+    (unit_oicr_targets_ex); the plain form keeps its own export, so a model without the branch launches what it always did.
+    wide (MODEL.LOAD_PROPOSALS): unit_oicr_targets_wide, up to max_weak_rows() rows per image instead of 1024, with or without the boxes"""
     rtot = rois5.shape[0]
+    if wide and (rtot != b * s or valid.numel() != rtot or src.shape[0] != rtot or multihot.numel() != b * k):
+        raise ValueError("oicr_targets: src, rois5 and valid need b * s rows, multihot b * k entries")
     labels = torch.empty((rtot,), dtype=torch.int32, device=src.device)
     weights = torch.empty((rtot,), dtype=torch.float32, device=src.device)
     args = (_p(src), src.shape[1], col0, mode, k, _p(rois5), _p(valid), s, b, _p(multihot), float(fg_thresh), float(bg_thresh), _p(labels),
             _p(weights))
+    if wide:
+        boxes = torch.empty((rtot, 4), dtype=torch.float32, device=src.device) if want_boxes else None
+        check(lib().unit_oicr_targets_wide(*args, _p(boxes), _s()), "oicr_targets_wide")
+        return (labels, weights, boxes) if want_boxes else (labels, weights)
     if not want_boxes:
         check(lib().unit_oicr_targets(*args, _s()), "oicr_targets")
         return labels, weights
